@@ -26,6 +26,11 @@ Run:  python bench.py [--gpus N --steps K --warmup W] [--workload flat1m|slab1b]
       process per GPU, RCCL); started directly with --gpus N it re-launches
       itself that way (before touching any GPU) and exits with its status.
       --dry-run: CPU-only rehearsal of the launch and the exchange (gloo).
+      A plain run sets up, warms up, times the K steps and prints the line.
+      --full adds every other leg and check (the oracle check of the last
+      step, the no-reuse leg, BASELINE configs 2-5, the scale legs, the CPU
+      baseline).  --dump-outputs DIR writes the last timed step's results as
+      DIR/<name>.npy so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -70,6 +75,13 @@ def parse(argv=None):
     ap.add_argument("--profile-run", action="store_true",
                     help="only the timed headline launches (no no-reuse leg, read probe or CPU baseline), so a "
                          "rocprofv3 --stats summary of the scan kernel covers exactly the launches `roofline` times")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the line can carry: the oracle check of the "
+                         "last step's results, the no-reuse leg and read ceiling, the --configs and --scale-legs "
+                         "legs and the CPU baseline (a plain run does the headline only and leaves those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (what the caller of the timed path receives) to "
+                         "DIR/ids.npy (float64), DIR/dists.npy (float32) and DIR/counts.npy (float64)")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only rehearsal of the N-rank launch + exchange")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal: all ranks on cuda:0 with a gloo exchange (one-GPU boxes; not a measurement)")
@@ -862,6 +874,22 @@ def run_configs(args, dev, torch):
 
 
 # ---------------------------------------------------------------------------
+def dump_outputs(path, ids, dists, counts):
+    """--dump-outputs: the last timed step's results as the caller receives
+    them -- ids [B][k] (docIDs, exact in float64), dists [B][k] float32,
+    counts [B] -- one .npy each (a few KB at the default shapes)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ids.npy"), np.asarray(ids).view(np.uint64).astype(np.float64))
+    np.save(os.path.join(path, "dists.npy"), np.asarray(dists, np.float32))
+    np.save(os.path.join(path, "counts.npy"), np.asarray(counts).astype(np.float64))
+
+
+def _unpack_block(blk_h, B, k):
+    """ids [B][k] and dists [B][k] of one packed top-k block copied to the host."""
+    return (blk_h[:B * k * 8].view(np.uint64).reshape(B, k),
+            blk_h[B * k * 8:B * k * 12].view(np.float32).reshape(B, k))
+
+
 def _timed(fn, dist, world, dev, torch):
     """Barrier + synchronize on both sides of fn(); returns the max over ranks."""
     torch.cuda.synchronize(dev)
@@ -1049,16 +1077,21 @@ def run_flat1m(args, world, rank, dev, torch, dist):
     q0 = (last * B) % P
     mcheck = None
     if world > 1:
-        if rank == 0:
-            mcheck = merge_check([(r * cap, n) for r in range(world)], d, k, qs[q0:q0 + 2],
-                                 m_ids[last % 2][:2].cpu().numpy(), m_d[last % 2][:2].cpu().numpy())
+        if rank == 0 and (args.full or args.dump_outputs):
+            got_i, got_d = m_ids[last % 2].cpu().numpy(), m_d[last % 2].cpu().numpy()
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, got_i, got_d, m_c[last % 2].cpu().numpy())
+            if args.full:
+                mcheck = merge_check([(r * cap, n) for r in range(world)], d, k, qs[q0:q0 + 2], got_i[:2], got_d[:2])
         dist.barrier()
-    else:
-        blk_h = send[last % 2].cpu().numpy()
-        got_i = blk_h[:B * k * 8].view(np.uint64).reshape(B, k)
-        got_d = blk_h[B * k * 8:B * k * 12].view(np.float32).reshape(B, k)
-        mcheck = merge_check([(0, n)], d, k, qs[q0:q0 + B], got_i, got_d)
-        mcheck["what"] = f"the last timed launch's {B} queries (scan_f32_stream_kernel's packed block)"
+    elif args.full or args.dump_outputs:
+        got_i, got_d = _unpack_block(send[last % 2].cpu().numpy(), B, k)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got_i, got_d, counts.cpu().numpy())
+        if args.full:
+            mcheck = merge_check([(0, n)], d, k, qs[q0:q0 + B], got_i, got_d)
+            mcheck["what"] = f"the last timed launch's {B} queries (scan_f32_stream_kernel's packed block)"
+    extras = args.full and not args.profile_run  # the untimed legs after the headline
 
     total_queries = world * B * args.steps  # 1M-row query scans over all GPUs
     avg_launch_s = scan_ms.value / 1e3 / max(1, launches.value)
@@ -1067,7 +1100,7 @@ def run_flat1m(args, world, rank, dev, torch, dist):
     traffic, traffic_src = stored_traffic(n, d, B)  # per launch, like `achieved`
     # untimed: the same kernel with no reuse between scans, and the HBM read ceiling
     nr_rows = max(n, args.no_reuse_rows)
-    if args.profile_run:
+    if not extras:
         nr_launch_s, ceiling, achieved_nr = float("nan"), float("nan"), float("nan")
     else:
         nr_launch_s, ceiling = no_reuse_leg(args, dev, torch, nr_rows, d, k, B, tq, P, max(4, min(args.steps, 10)))
@@ -1080,6 +1113,7 @@ def run_flat1m(args, world, rank, dev, torch, dist):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "full": bool(args.full),  # false: headline only; merge_check, *_no_reuse, ceiling, configs, cpu_baseline null
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1108,13 +1142,13 @@ def run_flat1m(args, world, rank, dev, torch, dist):
             "queries_per_launch": B,
             "algorithmic_bytes_per_launch": bytes_per_launch,
             "launches": int(launches.value),
-            "achieved_no_reuse": None if args.profile_run else round(achieved_nr, 1),
-            "frac_no_reuse": None if args.profile_run else round(achieved_nr / HBM_PEAK_GBS, 4),
-            "avg_launch_us_no_reuse": None if args.profile_run else round(nr_launch_s * 1e6, 2),
+            "achieved_no_reuse": None if not extras else round(achieved_nr, 1),
+            "frac_no_reuse": None if not extras else round(achieved_nr / HBM_PEAK_GBS, 4),
+            "avg_launch_us_no_reuse": None if not extras else round(nr_launch_s * 1e6, 2),
             "rows_no_reuse": nr_rows,
-            "ceiling_GBps": None if args.profile_run else round(ceiling, 1),
+            "ceiling_GBps": None if not extras else round(ceiling, 1),
             "frac_of_ceiling_no_reuse": (round(achieved_nr / ceiling, 4)
-                                         if not args.profile_run and ceiling > 0 else None),
+                                         if extras and ceiling > 0 else None),
             "gpu_clock": gpu_clock(dev, torch),
             "note": ("`achieved` = ALGORITHMIC bytes (N*d*4 per query scan, every query a full scan) / the "
                      "kernel's average launch time, Infinity-Cache reuse included: consecutive scans alternate "
@@ -1131,7 +1165,7 @@ def run_flat1m(args, world, rank, dev, torch, dist):
         "merge_check": mcheck,
     }
     legs = {}
-    if args.scale_legs and not args.profile_run:
+    if args.scale_legs and extras:
         # BASELINE configs[4] and configs[3] as strong scaling at this N (every rank takes part)
         for name in args.scale_legs.split(","):
             t0 = time.perf_counter()
@@ -1151,11 +1185,11 @@ def run_flat1m(args, world, rank, dev, torch, dist):
                 legs[f"{name}_error"] = f"{type(e).__name__}: {e}"
             if rank == 0:
                 print(f"bench.py: scale leg {name} {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
-    if rank == 0 and world == 1 and args.configs and not args.profile_run:
+    if rank == 0 and world == 1 and args.configs and extras:
         out["configs"] = run_configs(args, dev, torch)
     if legs:
         out["configs"] = dict(out["configs"] or {}, **legs)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_run:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and extras:
         cq = np.random.default_rng(43).uniform(-1, 1, (16, d)).astype(np.float32)
         gids, _, _ = corpus.search(cq, k)  # GPU results of the baseline's first queries (full-size cross-check)
 
@@ -1254,7 +1288,8 @@ def multi_handle_leg(world, rank, dist, rows_per_gpu=1_000_000, d=128, k=10, B=1
     return out
 
 
-def slab1b_leg(world, rank, dev, torch, dist, total=1_000_000_000, d=128, k=100, B=8, steps=2, W=1):
+def slab1b_leg(world, rank, dev, torch, dist, total=1_000_000_000, d=128, k=100, B=8, steps=2, W=1,
+               verify=True, dump=None):
     """BASELINE configs[4] at N GPUs (strong scaling): the 1B x 128 fp32 L2
     corpus as 8 slabs of 125M rows dealt to the N ranks (8/N each).  A GPU
     holds one slab in HBM at a time, regenerated in place between slabs
@@ -1264,7 +1299,8 @@ def slab1b_leg(world, rank, dev, torch, dist, total=1_000_000_000, d=128, k=100,
     RCCL all-gather + device merge (Index.objectVectorSearch's shard merge,
     adapters/repos/db/index.go:1567-1648).  At N = 1 all 8 slabs are scanned
     and merged: QPS_1 is measured, not derived.  Returns the measurements; rank
-    0 checks the last step's merged lists on sampled rows."""
+    0 checks the last step's merged lists on sampled rows (verify) and writes
+    them to the directory `dump` when one is given."""
     import ctypes
 
     from weaviate_amd._lib import KIND_F32, METRIC_L2, check
@@ -1335,13 +1371,15 @@ def slab1b_leg(world, rank, dev, torch, dist, total=1_000_000_000, d=128, k=100,
     merge_s = _timed(merge_all, dist, world, dev, torch)
     elapsed = scan_s + merge_s
     mcheck = None
-    if rank == 0:  # the last step's merged lists (untimed)
+    if rank == 0 and (verify or dump):  # the last step's merged lists (untimed)
         if world > 1:
-            gi, gd = m_ids[steps - 1][:2].cpu().numpy(), m_d[steps - 1][:2].cpu().numpy()
+            gi, gd = m_ids[steps - 1].cpu().numpy(), m_d[steps - 1].cpu().numpy()
         else:  # one GPU: the local merge wrote the packed block (ids [B][k], then dists)
-            blkh = send[steps - 1].cpu().numpy()
-            gi = blkh[:B * k * 8].view(np.uint64).reshape(B, k)[:2]
-            gd = blkh[B * k * 8:B * k * 12].view(np.float32).reshape(B, k)[:2]
+            gi, gd = _unpack_block(send[steps - 1].cpu().numpy(), B, k)
+        if dump:
+            dump_outputs(dump, gi, gd, m_c[steps - 1].cpu().numpy())
+    if rank == 0 and verify:
+        gi, gd = gi[:2], gd[:2]
         q2 = qs[(steps - 1) * B:(steps - 1) * B + 2].cpu().numpy()
         if total <= MERGE_CHECK_MAX_ROWS:
             mcheck = merge_check([(s * per, max(0, min(per, total - s * per))) for s in range(S)], d, k, q2, gi, gd)
@@ -1475,7 +1513,8 @@ def pq_sharded_leg(world, rank, dev, torch, dist, n=100_000_000, d=128, m=32, ks
 def run_slab1b(args, world, rank, dev, torch, dist):
     if 8 % world:
         raise SystemExit(f"bench.py: slab1b deals 8 slabs evenly, --gpus must divide 8")
-    r = slab1b_leg(world, rank, dev, torch, dist, args.rows, args.dim, args.k, args.batch, args.steps, args.warmup)
+    r = slab1b_leg(world, rank, dev, torch, dist, args.rows, args.dim, args.k, args.batch, args.steps, args.warmup,
+                   verify=args.full, dump=args.dump_outputs)
     total, d, k = args.rows, args.dim, args.k
     return {
         "metric": METRIC,

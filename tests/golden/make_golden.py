@@ -12,6 +12,9 @@ hamming.npz         seeded vector pairs (lengths 1..1536) with equal elements,
                     NaNs and signed zeros placed in the SIMD blocks and in the
                     scalar tail, with the outputs of the reference's own
                     hamming_256 / hamming_512 (D/c/hamming_avx{256,512}_amd64.c).
+flat_search_ref.npz the oracle's flat search (3000 x 128 seeded rows, k = 10, L2)
+                    run with the reference's compiled l2_256 as its distance
+                    kernel: the ids and distances it returned.
 known_answers.json  the hand-vector known answers of the reference's Go
                     tests (values transcribed as data, file:line cited).
 
@@ -106,6 +109,23 @@ def make_hamming():
                         lens=np.asarray(lens, np.int64), **{s: np.asarray(v, np.float32) for s, v in out.items()})
 
 
+FLAT_SEARCH = dict(row_seed=5, query_seed=6, rows=3000, dim=128, k=10)  # tests/test_oracle.py uses the same
+
+
+def make_flat_search():
+    """The result of the oracle's flat search when the reference's compiled
+    l2_256 computes its distances (the rows and the query come from the
+    counter RNG, so only the result is stored)."""
+    if wv_oracle.ref() is None:
+        raise SystemExit("oracle/_ref/libwvref.so missing: run `make -C oracle ref`")
+    p = FLAT_SEARCH
+    rows = wv_oracle.synth_rows(p["row_seed"], 0, p["rows"], p["dim"], 0)
+    q = wv_oracle.synth_rows(p["query_seed"], 0, 1, p["dim"], 0)[0]
+    ids, dists = wv_oracle.flat_search(rows, q, p["k"], wv_oracle.L2, use_ref_kernel=True)[:2]
+    np.savez_compressed(os.path.join(HERE, "flat_search_ref.npz"), ids=np.asarray(ids, np.uint64),
+                        dists=np.asarray(dists, np.float32))
+
+
 KNOWN = {
     "source": "reference Go tests, transcribed as data",
     "l2": [  # D/l2_test.go:21-66
@@ -153,6 +173,7 @@ KNOWN = {
 def main():
     make_distances()
     make_hamming()
+    make_flat_search()
     with open(os.path.join(HERE, "known_answers.json"), "w") as f:
         json.dump(KNOWN, f, indent=1)
     print("wrote", os.listdir(HERE))

@@ -196,14 +196,18 @@ def test_synthetic_generator_is_stable(orc):
 
 def test_flat_search_oracle_with_reference_kernel(orc):
     """The oracle's flat search gives the same results whether it calls its own
-    restated l2_256 or the reference's compiled l2_256 (when available)."""
-    if orc.ref() is None:
-        pytest.skip("oracle/_ref not built here")
+    restated l2_256 or the reference's compiled l2_256: against the stored
+    result of a run with the compiled kernel (tests/golden/make_golden.py),
+    and against the compiled kernel itself where oracle/_ref was built."""
+    g = np.load(os.path.join(GOLDEN, "flat_search_ref.npz"))
     rows = orc.synth_rows(5, 0, 3000, 128, 0)
     q = orc.synth_rows(6, 0, 1, 128, 0)[0]
     a = orc.flat_search(rows, q, 10, orc.L2)
-    b = orc.flat_search(rows, q, 10, orc.L2, use_ref_kernel=True)
-    assert np.array_equal(a[0], b[0]) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    assert len(g["ids"]) == 10
+    assert np.array_equal(a[0], g["ids"]) and np.array_equal(_bits(a[1]), _bits(g["dists"]))
+    if orc.ref() is not None:
+        b = orc.flat_search(rows, q, 10, orc.L2, use_ref_kernel=True)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(_bits(a[1]), _bits(b[1]))
 
 
 def test_oracle_kmeans_fit_properties():

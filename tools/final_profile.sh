@@ -20,9 +20,9 @@ step() {  # step <limit> <name> <cmd...>
   tail -n 5 "$O/$name.log"
   [ $rc -eq 0 ] || exit $rc
 }
-step 300 bench python3 bench.py
+step 300 bench python3 bench.py --full
 grep '^{' $O/bench.log | tail -1 > $O/bench.json
-step 300 trace rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --no-cpu-baseline
+step 300 trace rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --no-cpu-baseline
 step 300 pmc_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline
 step 600 configs rocprofv3 --kernel-trace --stats --output-format csv -d $O/configs_trace -- python3 tools/bench_configs.py
 step 120 pmc_pq rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU --kernel-trace --output-format csv -d $O/pmc_pq -- python3 tools/bench_configs.py --only pq --scale 0.25

@@ -22,7 +22,7 @@ step() {  # step <limit> <name> <cmd...>
   tail -n 3 "$O/$name.log"
   [ $rc -eq 0 ] || exit $rc
 }
-step 300 bench python3 bench.py
+step 300 bench python3 bench.py --full
 grep '^{' $O/bench.log | tail -1 > $O/bench.json
 step 300 trace rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --profile-run
 step 200 pmc_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 bench.py --steps 10 --warmup 2 --profile-run

@@ -20,9 +20,9 @@ step() {  # step <limit> <name> <cmd...>
   tail -n 3 "$O/$name.log"
   [ $rc -eq 0 ] || exit $rc
 }
-step 300 bench python3 bench.py
+step 300 bench python3 bench.py --full
 grep '^{' $O/bench.log | tail -1 > $O/bench.json
-step 420 trace rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py
+step 420 trace rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 bench.py --full
 grep '^{"metric"' $O/trace.log | tail -1 > $O/trace_bench.json
 python3 tools/trace_launch_avg.py "$(find $O/trace -name '*kernel_trace.csv' | head -1)" $O/trace_bench.json \
   --keep $O/trace_headline_dispatches.csv > $O/trace_vs_events.json

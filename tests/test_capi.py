@@ -148,3 +148,53 @@ def test_hot_kernels_use_no_scratch(tmp_path):
     bad = [n for n in bad if not any(k in n for k in known)]
     assert seen > 20, seen
     assert not bad, bad
+
+
+K1_FAMILIES = ("scan_f32_kernel", "scan_f32_stream_kernel", "scan_f32_mq_kernel", "scan_f32_qlist_kernel")
+
+
+def _k1_instantiations(lib_path, tmp_path, readelf):
+    """{(family, (metric, D, E, ...))} of the K1 kernels in the library's gfx950 code
+    objects, parsed from the mangled kernel names (...kernelILi<metric>ELi<D>ELi<E>E...)."""
+    import subprocess
+
+    found = set()
+    for j, co in enumerate(_gfx950_code_objects(lib_path)):
+        f = tmp_path / f"k1co{j}.o"
+        f.write_bytes(co)
+        notes = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True).stdout
+        for ln in notes.splitlines():
+            ln = ln.strip()
+            if not ln.startswith(".name:"):
+                continue
+            m = re.search(r"\d+(scan_f32_(?:stream_|mq_|qlist_)?kernel)I((?:L[ib]\d+E)+)E", ln)
+            if m:
+                found.add((m.group(1), tuple(int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2)))))
+    return found
+
+
+def test_k1_matrix_covers_every_specialization(tmp_path):
+    """The fixed row lengths and register-list sizes the K1 kernels are compiled for are
+    exactly those tests/test_gpu_k1_matrix.py runs against the oracle: a new `case <D>:`
+    of the scan dispatch fails here until the matrix has a row for it.  The last loop
+    also pins that every family is built for every metric kernel and list size: pruning
+    instantiations (e.g. the scan_f32_qlist_kernel forms without a caller,
+    profiles/r07/k1_matrix/README.md) means updating it."""
+    from test_gpu_k1_matrix import DIMS, K1
+    from weaviate_amd import _lib
+
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not os.path.exists(readelf):
+        pytest.skip("llvm-readelf not available")
+    found = _k1_instantiations(_lib.LIB_PATH, tmp_path, readelf)
+    assert {f for f, _ in found} == set(K1_FAMILIES)
+    fixed = set(K1["fixed_d"])
+    assert fixed <= set(DIMS) and any(d not in fixed for d in DIMS)  # every fixed length and a generic one are run
+    assert {a[1] for _, a in found} == fixed | {0}
+    for fam in ("scan_f32_kernel", "scan_f32_stream_kernel"):
+        assert {a[1] for f, a in found if f == fam} == fixed | {0}, fam
+    assert {a[2] for _, a in found} == set(K1["e"]) == {1, 2, 4}
+    assert {a[1] for f, a in found if f == "scan_f32_mq_kernel"} == set(K1["mq_d"]) == {128, 768}
+    for fam in K1_FAMILIES:  # every family in every list size and metric kernel (K1Q: L2 / dot only)
+        assert {a[0] for f, a in found if f == fam} == ({0, 1} if fam == "scan_f32_mq_kernel" else {0, 1, 3, 4}), fam
+        assert {a[2] for f, a in found if f == fam} == {1, 2, 4}, fam

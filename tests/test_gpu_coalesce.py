@@ -232,7 +232,10 @@ def test_coalesced_calls_with_concurrent_writes(ctx, orc):
     c.destroy()
 
 
-@pytest.mark.parametrize("metric,d", [(METRIC_L2, 128), (METRIC_COSINE, 96)])
+K100_CASES = {(METRIC_DOT, 768), (METRIC_COSINE, 128)}
+
+
+@pytest.mark.parametrize("metric,d", [(METRIC_L2, 128), (METRIC_COSINE, 96), (METRIC_DOT, 768), (METRIC_COSINE, 128)])
 def test_filtered_calls_coalesce_equal_serial(ctx, orc, metric, d):
     """Filtered single queries (every Weaviate query with a where-filter carries
     its own allow list: adapters/repos/db/shard_read.go:341, the scan
@@ -240,8 +243,10 @@ def test_filtered_calls_coalesce_equal_serial(ctx, orc, metric, d):
     co-scheduled K1 launch over the union of their allow windows, each query
     masked by its own (ScanArgs::allow_qstride).  16 threads with mixed lists
     -- 10 %, 1 %, a narrow id range, a single id, an empty list, none -- and
-    mixed k must get exactly what serial calls return."""
-    _filtered_vs_serial(ctx, orc, metric, d)
+    mixed k must get exactly what serial calls return.  The dot d = 768 and
+    cosine d = 128 cases call with k = 100 throughout: K1Q's filtered form at
+    d = 768 and with two-register lists."""
+    _filtered_vs_serial(ctx, orc, metric, d, k_all=100 if (metric, d) in K100_CASES else None)
 
 
 def test_filtered_calls_coalesce_with_mfma_min_queries_1(orc):
@@ -260,7 +265,7 @@ def test_filtered_batches_stay_within_the_byte_budget(ctx, orc):
     _filtered_vs_serial(ctx, orc, METRIC_L2, 32, n=1_200_000, nq=160, threads=80, wide=True)
 
 
-def _filtered_vs_serial(ctx, orc, metric, d, n=30_000, nq=96, threads=16, wide=False):
+def _filtered_vs_serial(ctx, orc, metric, d, n=30_000, nq=96, threads=16, wide=False, k_all=None):
     from weaviate_amd.device import allow_bitmap
 
     c = make_corpus(ctx, orc, KIND_F32, metric, n, d)
@@ -285,7 +290,7 @@ def _filtered_vs_serial(ctx, orc, metric, d, n=30_000, nq=96, threads=16, wide=F
             allows.append(np.zeros((n + 63) // 64, np.uint64))  # non-nil, empty: no results
         else:
             allows.append(None)
-    ks = [(10, 3, 10, 64, 10, 1)[(i // 6) % 6] for i in range(nq)]
+    ks = [k_all or (10, 3, 10, 64, 10, 1)[(i // 6) % 6] for i in range(nq)]
 
     def call(i):
         ids = np.empty(ks[i], np.uint64)
@@ -326,7 +331,7 @@ def _filtered_vs_serial(ctx, orc, metric, d, n=30_000, nq=96, threads=16, wide=F
     rows = orc.synth_rows(701, 0, n, d, 0)
     live = np.ones(n, bool)
     live[np.arange(5, n, 97)] = False
-    om = 2 if metric == METRIC_COSINE else 0
+    om = {METRIC_L2: 0, METRIC_DOT: 1, METRIC_COSINE: 2}[metric]  # the oracle's metric ids
     for i in range(0, nq, 7):
         a = allows[i]
         ok = live.copy()

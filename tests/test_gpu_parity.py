@@ -110,7 +110,7 @@ def test_flat_search_parity(ctx, orc, metric, d):
     c = Corpus(ctx, KIND_F32, metric, d, n)
     c.upsert(np.arange(n, dtype=np.uint64), rows)
     srows = stored_rows(orc, metric, rows)
-    for k in [1, 10, 64, 65, 100, 256]:
+    for k in [1, 10, 64, 65, 100, 128, 129, 256]:
         ids, dists, counts = c.search(qs, k)
         for qi in range(len(qs)):
             all_d = orc.dist_all(ORC_METRIC[metric], prep_query(orc, metric, qs[qi]), srows)

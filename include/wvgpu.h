@@ -75,9 +75,11 @@ typedef struct wvg_options {
                                   smaller ones run one HBM-bound scan per query.  0 = never.  Default 32. */
     int32_t cache_reuse;       /* 1 (default): consecutive scans of a corpus alternate direction and read
                                   the last ~320 MB of each pass with the default cache policy, so the next
-                                  scan starts on rows still in the 256 MiB Infinity Cache.  0: streaming --
-                                  one direction, non-temporal loads, no reuse between scans (e.g. next to
-                                  other memory-heavy work, or to measure the DRAM-bound rate). */
+                                  scan starts on rows still in the 256 MiB Infinity Cache; the queries of a
+                                  wvg_search_device_pipelined call share each row read.  0: streaming --
+                                  one direction, non-temporal loads, no reuse between scans: one full scan
+                                  per query (e.g. next to other memory-heavy work, or to measure the
+                                  DRAM-bound rate). */
     uint32_t merge_wait_us;    /* bound on the in-launch merge's wait for one query's scan workgroups
                                   (wvg_search_device_pipelined); 0 = the default, 4 s.  On expiry the
                                   query gets empty results and wvg_search_device_check fails. */
@@ -280,12 +282,19 @@ size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k);
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                       uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
                       size_t workspace_bytes, void *stream);
-/* nq independent single-query searches (each one full scan of the corpus:
- * flat.SearchByVector per query, as concurrent Weaviate queries issue them)
- * in ONE launch: the scan workgroups walk the queries back to back and one
- * extra workgroup merges each query's partial lists while the scan moves
- * on, so the merges cost no launches of their own.  F32 corpora; same
- * workspace size rule; outputs as wvg_search_device.                       */
+/* nq single-query searches (flat.SearchByVector per query, as concurrent
+ * Weaviate queries issue them) in ONE launch.  The results are those of nq
+ * independent searches, bit for bit.  Where the shared-row kernel applies
+ * -- nq >= 2, an L2 / dot / cosine corpus of d = 128 or 768 in the AVX2
+ * distance order, cache_reuse on -- the rows are read once per pass of up to
+ * 16 queries (k <= 64; 8 for k <= 128, 4 above; d = 768: 4, 2 above 128) and
+ * every query of the pass is scored against each row while it is in
+ * registers; one merge workgroup per query merges its partial lists in the
+ * same launch.  Everywhere else (one query, other metrics or dims,
+ * cache_reuse = 0) every query is one full scan of the corpus: the scan
+ * workgroups walk the queries back to back and one extra workgroup merges
+ * each query's lists while the scan moves on.  F32 corpora; same workspace
+ * size rule; outputs as wvg_search_device.                                 */
 int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                                 uint64_t *d_ids, float *d_dists, uint32_t *d_counts,
                                 void *d_workspace, size_t workspace_bytes, void *stream);

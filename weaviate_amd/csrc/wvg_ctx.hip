@@ -564,6 +564,12 @@ int wvgx_set_tuning(int key, int value)
     } else if (key == 33) {
         old = t.screen_round;
         t.screen_round = value;
+    } else if (key == 34) {
+        old = t.qshare;
+        t.qshare = value;
+    } else if (key == 35 && value >= 0) {
+        old = t.qshare_mergers;
+        t.qshare_mergers = value;
     }
     return old;
 }

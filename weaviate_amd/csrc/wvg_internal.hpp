@@ -284,11 +284,14 @@ inline int pq_cosched_groups(uint32_t nq, int num_cus)
     return 8 * (g > 0 ? g : 1);
 }
 hipError_t launch_scan_f32(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s);
-// Query-stream K1 (wvg_search_device_pipelined): ONE launch scans a.nq queries
-// back to back, every query a full scan of the corpus.  `groups` scan
-// workgroups loop over the queries, publishing each query's partial list with
-// a release + arrival count; one more workgroup waits for each query's
-// `groups` arrivals and merges it while the scan proceeds to the next query.
+// Query-stream K1 (wvg_search_device_pipelined): ONE launch answers a.nq queries;
+// the results are those of a.nq independent searches.  Where the shared-row
+// kernel applies (QShareArgs below) the rows are read once per pass of up to
+// qshare_queries_per_pass() queries.  Everywhere else (StreamJob) every query is
+// a full scan of the corpus: `groups` scan workgroups loop over the queries,
+// publishing each query's partial list with a write-through store + ready word;
+// one more workgroup merges each query's lists as they arrive while the scan
+// proceeds to the next query.
 // Sticky status word of a device-search workspace (its first bytes; read and
 // cleared by wvg_search_device_check).
 constexpr uint32_t WVG_STATUS_MERGE_TIMEOUT = 1u;
@@ -324,6 +327,36 @@ struct StreamJob {
     alignas(16) float qin[STREAM_QIN_FLOATS];
 };
 hipError_t launch_scan_f32_stream(const ScanArgs &a, const StreamJob &j, hipStream_t s);
+// Shared-row query stream (scan_f32_qshare_kernel): L2 / dot / cosine F32 corpora
+// of d = 128 or 768 in the AVX2 order, nq >= 2, no allow list.  One launch of
+// `groups` scan workgroups + `mergers` merge workgroups.  The queries are taken
+// qshare_queries_per_pass() at a time; a pass walks the wave's tiles once
+// (direction (reverse + pass) & 1) and scores every query of the pass against each
+// tile, then publishes one list per query: partials [nq][groups][k] with ready
+// words [nq][groups] (zeroed per call; 1 = published).  Merger m merges queries
+// m, m + mergers, ... with the bounded poll of merge_lists_ready; on expiry that
+// query gets empty results and WVG_STATUS_MERGE_TIMEOUT is set in *status.
+struct QShareArgs {
+    const void *data;        // tiled corpus
+    const uint64_t *valid;   // one word per tile
+    const float *queries;    // [nq][qpitch]
+    uint64_t *partials;
+    uint32_t *ready;
+    uint32_t *status;
+    uint64_t *ids;
+    float *dists;
+    uint32_t *counts;        // may be null
+    uint64_t id_base, tile_begin, tile_end;
+    uint64_t wait_limit;     // a merger's wait per query, s_memrealtime ticks (100 MHz)
+    uint32_t dim, qpitch, nq, k, groups;
+    uint32_t reverse;        // direction of pass 0
+    uint32_t plain, cache_tail256;  // as ScanArgs
+    int metric;
+};
+bool qshare_supported(int metric, uint32_t dim, int order512);
+uint32_t qshare_queries_per_pass(uint32_t dim, uint32_t k);
+uint32_t qshare_groups(uint64_t ntiles, int num_cus);
+hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s);
 // ids KEY_NONE, dists +inf, counts 0 for nq queries (empty corpus / slab).
 hipError_t launch_fill_empty(uint64_t *ids, float *dists, uint32_t *counts, uint32_t nq, uint32_t k, hipStream_t s);
 hipError_t launch_scan_bq(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s);
@@ -493,6 +526,11 @@ struct Tuning {
     int screen_pilot_screen = 0;  // K3c/K3d (tuning key 26): tiles of the SCREEN pilot -- the bf16 screen itself over
                                   // the first tiles in short ranges + one exact seed from their lists -- which
                                   // replaces the K3b pilot (0 = the K3b pilot; A/B)
+    int qshare = 0;          // wvg_search_device_pipelined's shared-row kernel (tuning key 34): 0 = where it applies,
+                             // -1 = never (one full scan per query, scan_f32_stream_kernel), 2 = its block shape
+                             // (4 queries per pass) at d = 128 too (A/B)
+    int qshare_mergers = 0;  // its merge workgroups (tuning key 35): 0 = one per query (at most 64), n = n (1 = the
+                             // queries merged one after another; A/B)
     int screen_diag = 0;     // K3c diagnostics (tools build only; results are NOT distances): bit 0 = no
                              // wait for the stage loads, bit 1 = no epilogue, bit 2 = no list insertions, bit 3 = no query-fragment loads (K3c); K3d: 1, 2, 4 or 16 (= counters) select compiled variants
 };

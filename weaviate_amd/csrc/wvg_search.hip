@@ -1285,6 +1285,32 @@ static StreamLayout stream_layout(const SearchPlan &p1, uint32_t nq, uint32_t k)
     return l;
 }
 
+// Workspace of the shared-row query stream (after the status block): partial
+// lists [nq][groups][k], then the ready words [nq][groups] (zeroed per call).
+struct QShareLayout {
+    size_t partials = 0, ready = 0, total = 0;
+    uint32_t groups = 0;
+};
+static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k)
+{
+    QShareLayout l;
+    l.groups = qshare_groups(p1.te - p1.tb, c->ctx->num_cus);
+    l.partials = WS_STATUS_BYTES;
+    l.ready = l.partials + align_up((size_t)nq * l.groups * k * 8, 256);
+    l.total = l.ready + align_up((size_t)nq * l.groups * 4, 256);
+    return l;
+}
+
+// wvg_search_device_pipelined takes the shared-row kernel for two or more
+// queries on a corpus it covers, in a context with cache_reuse on (cache_reuse = 0
+// means nothing is reused between scans: one full non-temporal scan per query).
+static bool qshare_route(const wvg_corpus *c, uint32_t nq)
+{
+    if (tuning().qshare < 0) return false;
+    return nq >= 2 && c->kind == WVG_KIND_F32 && c->ctx->opt.cache_reuse &&
+           qshare_supported(c->metric, c->dim, c->ctx->order512);
+}
+
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
 {
     if (!c) return 0;
@@ -1292,10 +1318,11 @@ size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
     SearchPlan p = plan_search(c, nq, k, nullptr, 0);
     const size_t dev = WS_STATUS_BYTES + align_up(p.workspace_bytes(nq, kk), 256) + device_query_bytes(c, nq);
     if (c->kind != WVG_KIND_F32) return dev;  // no pipelined mode
-    SearchPlan p1 = plan_search(c, 1, k, nullptr, 0);  // pipelined: two single-query buffers, or the stream layout
+    SearchPlan p1 = plan_search(c, 1, k, nullptr, 0);  // pipelined: two single-query buffers, or the stream layouts
     const size_t chain = 2 * align_up(p1.workspace_bytes(1, kk), 256);
     const size_t stream = stream_layout(p1, nq, kk).total;
-    return std::max({dev, WS_STATUS_BYTES + chain, stream});
+    const size_t shared = qshare_layout(c, p1, nq, kk).total;
+    return std::max({dev, WS_STATUS_BYTES + chain, stream, shared});
 }
 
 int wvg_search_device_check(wvg_ctx *ctx, void *d_workspace, void *stream)
@@ -1331,7 +1358,43 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
         WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));
         return WVG_OK;
     }
-    if (tuning().pipeline_mode == 1) {  // query-stream kernel: one launch for all nq queries (the product path)
+    if (tuning().pipeline_mode == 1 && qshare_route(c, nq)) {  // shared rows: one launch, rows read once per pass
+        const QShareLayout l = qshare_layout(c, p, nq, k);
+        if (!d_workspace || workspace_bytes < l.total) return fail(WVG_ERR_INVALID, "workspace too small");
+        char *w = (char *)d_workspace;
+        QShareArgs a{};
+        a.data = c->d_data;
+        a.valid = c->d_valid;
+        a.queries = d_queries;
+        a.partials = (uint64_t *)(w + l.partials);
+        a.ready = (uint32_t *)(w + l.ready);
+        a.status = (uint32_t *)w;
+        a.ids = d_ids;
+        a.dists = d_dists;
+        a.counts = d_counts;
+        a.id_base = c->id_base;
+        a.tile_begin = p.tb;
+        a.tile_end = p.te;
+        const uint32_t wait_us = tuning().merge_wait_us > 0 ? (uint32_t)tuning().merge_wait_us : c->ctx->opt.merge_wait_us;
+        a.wait_limit = wait_us > 0 ? (uint64_t)wait_us * 100ull : 400000000ull;
+        a.dim = c->dim;
+        a.qpitch = c->dim;
+        a.nq = nq;
+        a.k = k;
+        a.groups = l.groups;
+        const uint32_t qp = qshare_queries_per_pass(c->dim, k);
+        a.reverse = next_direction(c, (nq + qp - 1) / qp);  // one direction per pass
+        a.plain = plain_loads(c, p.tb, p.te);
+        a.cache_tail256 = k1_cache_tail(c, p.tb, p.te);
+        a.metric = c->metric;
+        const uint32_t mergers = tuning().qshare_mergers > 0 ? (uint32_t)tuning().qshare_mergers : std::min<uint32_t>(nq, 64);
+        WVG_HIP(hipMemsetAsync(a.ready, 0, l.total - l.ready, s));
+        ProfArm arm(c->ctx);
+        if (arm.rc) return arm.rc;
+        WVG_HIP(launch_scan_f32_qshare(a, mergers, s));
+        return WVG_OK;
+    }
+    if (tuning().pipeline_mode == 1) {  // query-stream kernel: one launch for all nq queries, a full scan each
         const StreamLayout l = stream_layout(p, nq, k);
         if (!d_workspace || workspace_bytes < l.total) return fail(WVG_ERR_INVALID, "workspace too small");
         char *w = (char *)d_workspace;

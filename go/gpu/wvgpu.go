@@ -1071,6 +1071,9 @@ func (x *MultiCorpus) SetCodebook(centers []float32, m, ks int) error {
 // all-gather of their top-k blocks, the merge (index.go:1644-1648).
 func (x *MultiCorpus) SearchBatch(qs []float32, nq, k int, allow helpers.AllowList) (*Results, error) {
 	defer pin(x)()
+	if len(qs) != nq*x.dims {
+		return nil, errors.Errorf("queries hold %d floats, want nq * dims = %d", len(qs), nq*x.dims)
+	}
 	r := emptyResults(nq, k)
 	if nq == 0 || k == 0 {
 		return r, nil
@@ -1080,6 +1083,56 @@ func (x *MultiCorpus) SearchBatch(qs []float32, nq, k int, allow helpers.AllowLi
 		return r, nil
 	}
 	if e := err(C.wvg_multi_search(x.h, f32p(qs), C.uint32_t(nq), C.uint32_t(k), u64p(words),
+		C.uint64_t(len(words)), u64p(r.IDs), f32p(r.Dists), u32p(r.Counts))); e != nil {
+		return nil, e
+	}
+	return r, nil
+}
+
+// SearchBQRescore: flat.searchByVectorBQ (V/flat/index.go:347-389) over a BQ
+// class dealt over the devices: x holds the codes, f32 the float rows (a multi
+// corpus of the same Multi with the same dims / metric / rows).  One heap of
+// max(rescoreLimit, k) over all slabs, the exact rescore on the owning slab,
+// the heap of k: the result of Corpus.SearchBQRescore on one corpus.
+func (x *MultiCorpus) SearchBQRescore(f32 *MultiCorpus, qs []float32, nq, k, rescoreLimit int,
+	allow helpers.AllowList) (*Results, error) {
+	defer pin(x, f32)()
+	if len(qs) != nq*x.dims {
+		return nil, errors.Errorf("queries hold %d floats, want nq * dims = %d", len(qs), nq*x.dims)
+	}
+	r := emptyResults(nq, k)
+	if nq == 0 || k == 0 {
+		return r, nil
+	}
+	words, ok := allowBitmap(allow)
+	if !ok {
+		return r, nil
+	}
+	if e := err(C.wvg_multi_search_bq_rescore(x.h, f32.h, f32p(qs), C.uint32_t(nq), C.uint32_t(k),
+		C.uint32_t(rescoreLimit), u64p(words), C.uint64_t(len(words)), u64p(r.IDs), f32p(r.Dists),
+		u32p(r.Counts))); e != nil {
+		return nil, e
+	}
+	return r, nil
+}
+
+// SearchBQCandidates: its first half (V/flat/index.go:355-374) for callers whose
+// float rows stay in the LSM store: the heap's candidates over all slabs in
+// heap.Pop() order, ids as global docIDs (see Corpus.SearchBQCandidates).
+func (x *MultiCorpus) SearchBQCandidates(qs []float32, nq, rescoreLimit int, allow helpers.AllowList) (*Results, error) {
+	defer pin(x)()
+	if len(qs) != nq*x.dims {
+		return nil, errors.Errorf("queries hold %d floats, want nq * dims = %d", len(qs), nq*x.dims)
+	}
+	r := emptyResults(nq, rescoreLimit)
+	if nq == 0 || rescoreLimit == 0 {
+		return r, nil
+	}
+	words, ok := allowBitmap(allow)
+	if !ok {
+		return r, nil
+	}
+	if e := err(C.wvg_multi_search_bq_candidates(x.h, f32p(qs), C.uint32_t(nq), C.uint32_t(rescoreLimit), u64p(words),
 		C.uint64_t(len(words)), u64p(r.IDs), f32p(r.Dists), u32p(r.Counts))); e != nil {
 		return nil, e
 	}

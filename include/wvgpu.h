@@ -31,7 +31,8 @@ extern "C" {
 /* 2: wvg_options gained `coalesce` (round 4) and the device-memory / stream
  * entry points were added (wvg_device_alloc ... wvg_memcpy_d2h).
  * 3: wvg_options gained `heap_replay`; wvg_search_bq_candidates; the
- * multi-GPU handle (wvg_multi_*). */
+ * multi-GPU handle (wvg_multi_*).  Added since without a version change
+ * (purely additive): wvg_multi_search_bq_rescore / _bq_candidates. */
 #define WVG_ABI_VERSION 3
 
 #define WVG_OK 0
@@ -358,6 +359,28 @@ int wvg_multi_corpus_set_codebook(wvg_multi_corpus *mc, const float *centers, ui
 int wvg_multi_search(wvg_multi_corpus *mc, const float *queries, uint32_t nq, uint32_t k,
                      const uint64_t *allow_bits, uint64_t allow_words, uint64_t *out_ids, float *out_dists,
                      uint32_t *out_counts);
+/* flat.searchByVectorBQ (V/flat/index.go:347-389, 456-506) over a BQ class
+ * dealt over the devices: `bq` and `f32` are a BQ and an F32 multi corpus of
+ * the same multi handle with the same dim, metric and slab.  Every slab runs
+ * the recording Hamming scan on its device; the slabs' distance histograms
+ * are exchanged (one grouped all-gather, or peer copies) so that slab s also
+ * drops what the R-th smallest distance of slabs 0..s-1 already excludes; the
+ * kept rows of all slabs, in docID order, go through ONE heap of R =
+ * max(rescore_limit, k) on the host, the popped ids are rescored exactly on
+ * the slab that owns them and inserted into the heap of k in pop order.
+ * Outputs as wvg_search_bq_rescore, and equal to it on one corpus holding
+ * every row.  Contexts opened with heap_replay = 0: WVG_ERR_UNSUPPORTED.    */
+int wvg_multi_search_bq_rescore(wvg_multi_corpus *bq, wvg_multi_corpus *f32, const float *queries,
+                                uint32_t nq, uint32_t k, uint32_t rescore_limit, const uint64_t *allow_bits,
+                                uint64_t allow_words, uint64_t *out_ids, float *out_dists,
+                                uint32_t *out_counts);
+/* Its first half (V/flat/index.go:347-389, 456-506; see
+ * wvg_search_bq_candidates): the heap's R = rescore_limit candidates over all
+ * slabs in the order heap.Pop() returns them, ids as global docIDs.  Outputs
+ * as wvg_search_bq_candidates.  heap_replay = 0: WVG_ERR_UNSUPPORTED.       */
+int wvg_multi_search_bq_candidates(wvg_multi_corpus *bq, const float *queries, uint32_t nq,
+                                   uint32_t rescore_limit, const uint64_t *allow_bits, uint64_t allow_words,
+                                   uint64_t *out_ids, float *out_dists, uint32_t *out_counts);
 
 /* The rescore loop of flat.searchByVectorBQ (V/flat/index.go:375-385) when
  * the candidate rows come from the host (LSM point gets): exact SingleDist of

@@ -112,6 +112,10 @@ SIGNATURES = {
     "wvg_multi_corpus_set_codebook": (c_int, [c_void_p, _P(c_float), c_uint32, c_uint32]),
     "wvg_multi_search": (c_int, [c_void_p, _P(c_float), c_uint32, c_uint32, _P(c_uint64), c_uint64,
                                  _P(c_uint64), _P(c_float), _P(c_uint32)]),
+    "wvg_multi_search_bq_rescore": (c_int, [c_void_p, c_void_p, _P(c_float), c_uint32, c_uint32, c_uint32,
+                                            _P(c_uint64), c_uint64, _P(c_uint64), _P(c_float), _P(c_uint32)]),
+    "wvg_multi_search_bq_candidates": (c_int, [c_void_p, _P(c_float), c_uint32, c_uint32, _P(c_uint64), c_uint64,
+                                               _P(c_uint64), _P(c_float), _P(c_uint32)]),
     "wvg_synthetic_rows": (c_int, [c_void_p, c_uint64, _P(c_uint64), c_uint64, c_uint32, c_int, c_int, _P(c_float)]),
     "wvg_profile_start": (c_int, [c_void_p]),
     "wvg_profile_stop": (c_int, [c_void_p, _P(ctypes.c_double), _P(c_uint64)]),

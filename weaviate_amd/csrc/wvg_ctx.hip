@@ -457,7 +457,8 @@ int wvgx_filtered_timing(uint64_t *out5, int reset)
 // 20 = screen kernel (0 K3d where it applies, 1 K3c), 21 = screen pilot seed, 22 = exact seeds between
 // screen phases, 23 = K3b pilot tiles, 24 = single-query host path, ..., 29 / 30 = K3i warm-up range
 // blocks (first / second phase), 31 = filtered batches' windows from pinned staging, 32 = K3i's K3b pilot tiles,
-// 33 = screen ranges in whole rounds of the CUs.  Returns the previous value.
+// 33 = screen ranges in whole rounds of the CUs, ..., 36 = the multi-GPU BQ flow's cross-slab bound.
+// Returns the previous value.
 int wvgx_set_tuning(int key, int value)
 {
     Tuning &t = tuning();
@@ -570,6 +571,9 @@ int wvgx_set_tuning(int key, int value)
     } else if (key == 35 && value >= 0) {
         old = t.qshare_mergers;
         t.qshare_mergers = value;
+    } else if (key == 36) {
+        old = t.multi_bq_bound;
+        t.multi_bq_bound = value;
     }
     return old;
 }

@@ -236,12 +236,48 @@ size_t replay_workspace_bytes(const wvg_corpus *bq, uint32_t nq, uint32_t R, con
 // for nq prepared BQ queries: pops[q] = (slot, Hamming distance) in pop order.
 int bq_heap_candidates(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq, uint32_t R,
                        const uint64_t *d_allow, const SearchPlan &p, char *ws, std::vector<std::vector<GoItem>> &pops);
+// Its steps, for callers that need the kept rows before the heap (the multi-GPU
+// flow, wvg_multi.hip): scan = the recording scan enqueued on the slot's stream
+// (the range lists are then at rp.partials()); filter = prefix thresholds, the
+// filter with an optional per-query device bound [nq] (null: none) and the
+// gather, enqueued on s; collect = totals and kept rows copied back (one
+// stream sync; a query whose buffers overflowed is rerun with the same bound)
+// and handed to sink(q, keys, n): n keys (ordered distance << 32 | slot),
+// ascending slot, valid only during the call.
+struct ReplayWs {
+    size_t part = 0, emit = 0, ecnt = 0, thr = 0, fcnt = 0, out = 0, tot = 0, total = 0;
+};
+struct ReplayPass {
+    wvg_ctx *ctx = nullptr;
+    ScanArgs a{};
+    int groups = 0;
+    uint32_t cap = 0, qpb = 0;
+    const void *d_qb = nullptr;
+    char *ws = nullptr;
+    ReplayWs w;
+    const uint64_t *partials() const { return (const uint64_t *)(ws + w.part); }
+};
+int replay_scan(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq, uint32_t R,
+                const uint64_t *d_allow, const SearchPlan &p, char *ws, ReplayPass &rp);
+int replay_filter(const ReplayPass &rp, const float *d_bound, hipStream_t s);
+int replay_collect(const ReplayPass &rp, StreamSlot *sl, const float *d_bound,
+                   const std::function<void(uint32_t, const uint64_t *, size_t)> &sink);
+#ifdef WVG_TOOLS
+std::atomic<uint64_t> &replay_rerun_count();
+#endif
+// findTopVectorsCached + the pop loop over rows given as (id, distance), ascending id.
+void replay_rows(const GoItem *rows, size_t n, uint32_t R, std::vector<GoItem> &pops);
 // The same for windows above MAX_K (wvg_range.hip): S1 keys, doubling chunks
 // with prefix-select thresholds, compaction, sort, the host heap.
 size_t select_replay_bytes(const SearchPlan &p);
 int bq_heap_candidates_select(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq,
                               uint32_t R, const uint64_t *d_allow, const SearchPlan &p, char *ws,
                               std::vector<std::vector<GoItem>> &pops);
+// Its kept rows before the heap: sink(q, keys, n) with n keys (slot << 32 |
+// ordered distance), ascending slot, valid only during the call.
+int bq_select_kept(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq, uint32_t R,
+                   const uint64_t *d_allow, const SearchPlan &p, char *ws,
+                   const std::function<void(uint32_t, const uint64_t *, size_t)> &sink);
 // searchByVectorBQ exactly (any R): the candidates above, their exact
 // distances on the device, the k-heap in pop order on the host.  f32 null:
 // outputs are the candidates themselves ([nq][R], pop order).

@@ -375,9 +375,20 @@ hipError_t launch_emit_prefix(const uint64_t *partials, uint32_t nq, uint32_t gr
                               hipStream_t s, uint32_t max_dist = 0);  // max_dist > 0: integer distances <= it
 hipError_t launch_emit_filter(uint64_t *emit, const uint32_t *emit_cnt, uint32_t emit_cap, const float *thr,
                               uint32_t nq, uint32_t groups, uint32_t waves_per_group, uint32_t *fcnt, uint32_t *oflow,
-                              hipStream_t s);
+                              hipStream_t s, const float *bound = nullptr);  // bound [nq]: d < min(thr, bound[q])
 hipError_t launch_emit_gather(const uint64_t *emit, const uint32_t *fcnt, uint32_t emit_cap, uint32_t nq,
                               uint32_t waves, uint64_t *out, uint32_t out_cap, uint32_t *totals, hipStream_t s);
+// The cross-slab bound of a BQ corpus dealt over several devices (wvg_replay.hip;
+// integer distances in [0, nbins)).  hist: per query the distance histogram of a
+// slab's range lists (partials [nq][groups][k]) into hist [nq][nbins].  bound:
+// from the gathered histograms [nslabs][nq][nbins], X[(s - s0) * nq + q] for
+// slabs s0 .. s0 + ns - 1 = the smallest distance whose count over slabs < s
+// reaches R, +inf while fewer than R rows precede the slab.
+bool slab_hist_fits(uint32_t nbins);
+hipError_t launch_slab_hist(const uint64_t *partials, uint32_t nq, uint32_t groups, uint32_t k, uint32_t nbins,
+                            uint32_t *hist, hipStream_t s);
+hipError_t launch_slab_bound(const uint32_t *hists, uint32_t nq, uint32_t nbins, uint32_t R, uint32_t s0, uint32_t ns,
+                             float *X, hipStream_t s);
 hipError_t launch_scan_pq(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s);
 // The exact K1 rescan of a device-resident query list (qlist[0 .. *nlist)),
 // `slots` queries in flight: partials [f][groups][k]; and its merge.
@@ -531,6 +542,8 @@ struct Tuning {
                              // (4 queries per pass) at d = 128 too (A/B)
     int qshare_mergers = 0;  // its merge workgroups (tuning key 35): 0 = one per query (at most 64), n = n (1 = the
                              // queries merged one after another; A/B)
+    int multi_bq_bound = 1;  // multi-GPU BQ heap flow (tuning key 36): 1 = the cross-slab bound X_s in the filter,
+                             // 0 = every slab filters with its own thresholds only (A/B: rows replayed)
     int screen_diag = 0;     // K3c diagnostics (tools build only; results are NOT distances): bit 0 = no
                              // wait for the stage loads, bit 1 = no epilogue, bit 2 = no list insertions, bit 3 = no query-fragment loads (K3c); K3d: 1, 2, 4 or 16 (= counters) select compiled variants
 };

@@ -232,9 +232,9 @@ size_t select_replay_bytes(const SearchPlan &p)
     return cv.off;
 }
 
-int bq_heap_candidates_select(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq,
-                              uint32_t R, const uint64_t *d_allow, const SearchPlan &p, char *ws,
-                              std::vector<std::vector<GoItem>> &pops)
+int bq_select_kept(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq, uint32_t R,
+                   const uint64_t *d_allow, const SearchPlan &p, char *ws,
+                   const std::function<void(uint32_t, const uint64_t *, size_t)> &sink)
 {
     hipStream_t s = sl->stream;
     const int cus = bq->ctx->num_cus;
@@ -246,7 +246,6 @@ int bq_heap_candidates_select(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, 
     SelectBufs sb;
     sb.bind(ws, o_sel, o_temp, temp_bytes);
     uint32_t *d_thr = (uint32_t *)(ws + o_thr);
-    pops.assign(nq, {});
     std::vector<uint64_t> keys;
     for (uint32_t qi = 0; qi < nq; qi++) {
         ScanArgs a1 = scan_args_for(bq, (const uint64_t *)d_qb + (size_t)qi * qpb, qpb, 1, R, d_allow, p.tb, p.te);
@@ -279,13 +278,23 @@ int bq_heap_candidates_select(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, 
         keys.resize(n);
         if (n) WVG_HIP(hipMemcpyAsync(keys.data(), sb.sorted, n * 8, hipMemcpyDeviceToHost, s));
         WVG_HIP(hipStreamSynchronize(s));
+        sink(qi, keys.data(), n);
+    }
+    return WVG_OK;
+}
+
+int bq_heap_candidates_select(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq,
+                              uint32_t R, const uint64_t *d_allow, const SearchPlan &p, char *ws,
+                              std::vector<std::vector<GoItem>> &pops)
+{
+    pops.assign(nq, {});
+    return bq_select_kept(bq, sl, d_qb, qpb, nq, R, d_allow, p, ws, [&](uint32_t qi, const uint64_t *keys, size_t n) {
         GoMaxHeap h(R);
-        for (uint64_t i = 0; i < n; i++)
+        for (size_t i = 0; i < n; i++)
             insert_to_heap(h, R, (uint32_t)(keys[i] >> 32), wvg_unord_f32((uint32_t)keys[i]));
         pops[qi].reserve(h.len());
         while (h.len()) pops[qi].push_back(h.pop());
-    }
-    return WVG_OK;
+    });
 }
 
 // How many of the ascending results SearchByVectorDistance returns, given

@@ -26,6 +26,11 @@
 // device (K6) and replays again into the k-heap.  A wave whose buffer
 // overflows (adversarial orders: distances falling with the docID) reruns its
 // query with full-size buffers, seeded with the first pass's thr.
+//
+// A corpus dealt over several devices in docID slabs (wvg_multi.hip) runs
+// steps 1-4 per slab with one more bound in step 3, X_s from the earlier
+// slabs' distance histograms ("the cross-slab bound" below), and replays the
+// slabs' survivors, concatenated in slab order, through one heap.
 #include "wvg_heap.hpp"
 #include "wvg_host.hpp"
 #include "wvg_topk.hpp"
@@ -289,10 +294,13 @@ hipError_t launch_emit_prefix(const uint64_t *partials, uint32_t nq, uint32_t gr
 
 // One wave per emitting wave: keep the keys with distance < thr of its range,
 // compacted in place (a chunk is read whole before any of it is overwritten,
-// and writes never pass the read position).
+// and writes never pass the read position).  bound (optional, [nq]): a second
+// upper bound of T_i that holds for every row of the call -- the cross-slab
+// X_s of a multi-GPU corpus (slab_bound_kernel); the test is then
+// d_i < min(thr[g], bound[q]).
 __global__ __launch_bounds__(256) void emit_filter_kernel(uint64_t *emit, const uint32_t *emit_cnt, uint32_t cap,
                                                           const float *thr, uint32_t groups, uint32_t wpg,
-                                                          uint32_t *fcnt, uint32_t *oflow)
+                                                          uint32_t *fcnt, uint32_t *oflow, const float *bound)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t waves = groups * wpg;
@@ -300,7 +308,8 @@ __global__ __launch_bounds__(256) void emit_filter_kernel(uint64_t *emit, const 
     if (w >= waves) return;
     const size_t src = (size_t)qi * waves + w;
     const uint32_t cnt = emit_cnt[src], n = min(cnt, cap);
-    const float tv = thr[(size_t)qi * groups + w / wpg];
+    float tv = thr[(size_t)qi * groups + w / wpg];
+    if (bound) tv = fminf(tv, bound[qi]);
     uint64_t *buf = emit + src * cap;
     uint32_t out = 0;
     for (uint32_t i = 0; i < n; i += 64) {
@@ -319,12 +328,12 @@ __global__ __launch_bounds__(256) void emit_filter_kernel(uint64_t *emit, const 
 
 hipError_t launch_emit_filter(uint64_t *emit, const uint32_t *emit_cnt, uint32_t emit_cap, const float *thr,
                               uint32_t nq, uint32_t groups, uint32_t waves_per_group, uint32_t *fcnt, uint32_t *oflow,
-                              hipStream_t s)
+                              hipStream_t s, const float *bound)
 {
     const uint32_t waves = groups * waves_per_group;
     if (nq == 0 || waves == 0) return hipSuccess;
     hipLaunchKernelGGL(emit_filter_kernel, dim3((waves + 3) / 4, nq), dim3(256), 0, s, emit, emit_cnt, emit_cap, thr,
-                       groups, waves_per_group, fcnt, oflow);
+                       groups, waves_per_group, fcnt, oflow, bound);
     return hipGetLastError();
 }
 
@@ -356,6 +365,96 @@ hipError_t launch_emit_gather(const uint64_t *emit, const uint32_t *fcnt, uint32
     if (nq == 0 || waves == 0) return hipSuccess;
     hipLaunchKernelGGL(emit_gather_kernel, dim3((waves + 3) / 4, nq), dim3(256), 0, s, emit, fcnt, emit_cap, waves,
                        out, out_cap, totals);
+    return hipGetLastError();
+}
+
+// ---- the cross-slab bound (a BQ corpus dealt over several devices) -------------
+//
+// Slabs are contiguous docID ranges, so for a row of slab s every live allowed
+// row of slabs 0..s-1 precedes it: X_s, the R-th smallest distance over those
+// rows (+inf while there are fewer than R, and for s = 0), is an upper bound
+// of T_i like thr[g] is, and slab s may drop every kept row with d_i >=
+// min(thr[g], X_s).  Hamming distances are integers in [0, nbins), so X_s
+// needs only each slab's distance histogram: slab_hist counts the entries of
+// the slab's per-range top-R lists (every entry is a real live allowed row and
+// their union holds the slab's R smallest, so no truncation is needed), the
+// histograms are exchanged, and slab_bound walks their sum over the earlier
+// slabs.  A histogram that does not fit one workgroup's LDS (nbins above
+// SLAB_HIST_MAX_BINS: rows of more than ~2M bits) skips the bound for that
+// call: X_s = +inf, the filter is the single-device one and the result is
+// unchanged, only more rows are replayed.  Windows above 256 (the select-based
+// superset, wvg_range.hip) use no cross-slab bound either.
+constexpr uint32_t SLAB_HIST_MAX_BINS = 16384;  // 64 KiB of LDS
+constexpr int SLAB_HIST_THREADS = 1024;
+
+// One workgroup per query: its LDS histogram over the slab's list entries.
+__global__ __launch_bounds__(SLAB_HIST_THREADS) void slab_hist_kernel(const uint64_t *partials, uint32_t groups,
+                                                                      uint32_t k, uint32_t nbins, uint32_t *hist)
+{
+    extern __shared__ uint32_t bins[];  // [nbins]
+    const uint32_t qi = blockIdx.x;
+    for (uint32_t b = threadIdx.x; b < nbins; b += SLAB_HIST_THREADS) bins[b] = 0u;
+    __syncthreads();
+    const uint64_t *pq = partials + (size_t)qi * groups * k;
+    const uint32_t n = groups * k;
+    for (uint32_t i = threadIdx.x; i < n; i += SLAB_HIST_THREADS) {
+        const uint64_t key = pq[i];
+        if (key == WVG_KEY_NONE) continue;
+        const float d = wvg_unord_f32((uint32_t)(key >> 32));
+        if (d >= 0.f && d < (float)nbins) atomicAdd(&bins[(uint32_t)d], 1u);
+    }
+    __syncthreads();
+    uint32_t *out = hist + (size_t)qi * nbins;
+    for (uint32_t b = threadIdx.x; b < nbins; b += SLAB_HIST_THREADS) out[b] = bins[b];
+}
+
+// One wave per (query, slab s): the first bin whose count, summed over the
+// slabs before s and cumulated over the bins, reaches R (a wave-wide inclusive
+// prefix sum per 64 bins, as emit_prefix_hist_kernel's find_v).
+__global__ __launch_bounds__(64) void slab_bound_kernel(const uint32_t *hists, uint32_t nq, uint32_t nbins, uint32_t R,
+                                                        uint32_t s0, float *X)
+{
+    const int lane = threadIdx.x & 63;
+    const uint32_t qi = blockIdx.x, s = s0 + blockIdx.y;
+    float x = __builtin_inff();
+    uint32_t base = 0;
+    for (uint32_t b0 = 0; b0 < nbins && s > 0; b0 += 64) {
+        const uint32_t b = b0 + (uint32_t)lane;
+        uint32_t c = 0;
+        if (b < nbins)
+            for (uint32_t t = 0; t < s; t++) c += hists[((size_t)t * nq + qi) * nbins + b];
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)c, off, 64);
+            if (lane >= off) c += o;
+        }
+        const uint64_t hit = __ballot(base + c >= R);
+        if (hit) {
+            x = (float)(b0 + (uint32_t)__builtin_ctzll(hit));
+            break;
+        }
+        base += (uint32_t)__shfl((int)c, 63, 64);
+    }
+    if (lane == 0) X[(size_t)blockIdx.y * nq + qi] = x;
+}
+
+bool slab_hist_fits(uint32_t nbins) { return nbins > 0 && nbins <= SLAB_HIST_MAX_BINS; }
+
+hipError_t launch_slab_hist(const uint64_t *partials, uint32_t nq, uint32_t groups, uint32_t k, uint32_t nbins,
+                            uint32_t *hist, hipStream_t s)
+{
+    if (nq == 0) return hipSuccess;
+    if (!slab_hist_fits(nbins)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slab_hist_kernel, dim3(nq), dim3(SLAB_HIST_THREADS), (size_t)nbins * 4, s, partials, groups, k,
+                       nbins, hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_slab_bound(const uint32_t *hists, uint32_t nq, uint32_t nbins, uint32_t R, uint32_t s0, uint32_t ns,
+                             float *X, hipStream_t s)
+{
+    if (nq == 0 || ns == 0) return hipSuccess;
+    hipLaunchKernelGGL(slab_bound_kernel, dim3(nq, ns), dim3(64), 0, s, hists, nq, nbins, R, s0, X);
     return hipGetLastError();
 }
 
@@ -397,10 +496,6 @@ EmitPlan emit_plan_for(uint64_t ntiles, int groups, uint32_t nq, uint32_t R, int
     return e;
 }
 
-struct ReplayWs {
-    size_t part = 0, emit = 0, ecnt = 0, thr = 0, fcnt = 0, out = 0, tot = 0, total = 0;
-};
-
 ReplayWs replay_ws(uint32_t nq, uint32_t groups, uint32_t R, uint32_t cap, uint32_t out_cap)
 {
     ReplayWs w;
@@ -417,31 +512,45 @@ ReplayWs replay_ws(uint32_t nq, uint32_t groups, uint32_t R, uint32_t cap, uint3
     return w;
 }
 
-// The four device steps over ScanArgs `a` (queries, allow window, k = R set),
-// into `ws` laid out by `w`; no host synchronization.
-int run_emit(wvg_ctx *ctx, const ScanArgs &a0, int groups, uint32_t cap, bool lds, uint32_t out_cap, char *ws,
-             const ReplayWs &w, const float *seed, hipStream_t s)
+// The recording scan over ScanArgs `a` (queries, allow window, k = R set) into
+// `ws` laid out by `w` (its range lists, per-wave records and counts); no host
+// synchronization.  `a` leaves with the record buffers set.
+int emit_scan(wvg_ctx *ctx, ScanArgs &a, int groups, uint32_t cap, bool lds, char *ws, const ReplayWs &w,
+              const float *seed, hipStream_t s)
 {
-    ScanArgs a = a0;
     a.emit = (uint64_t *)(ws + w.emit);
     a.emit_cnt = (uint32_t *)(ws + w.ecnt);
     a.emit_cap = cap;
     a.emit_seed = seed;
+    WVG_HIP(hipMemsetAsync(ws + w.tot, 0, (size_t)a.nq * 8, s));
+    ProfArm arm(ctx);  // wvg_profile_*: the scan dispatch's own events
+    if (arm.rc) return arm.rc;
+    WVG_HIP(launch_scan_bq_emit(a, (uint64_t *)(ws + w.part), groups, lds, s));
+    return WVG_OK;
+}
+
+// prefix, filter (with the optional per-query bound) and gather over a scan's records.
+int emit_finish(const ScanArgs &a, int groups, uint32_t cap, uint32_t out_cap, char *ws, const ReplayWs &w,
+                const float *bound, hipStream_t s)
+{
     const uint32_t nq = a.nq, R = a.k, waves = (uint32_t)groups * BQ_SCAN_WAVES;
     uint32_t *tot = (uint32_t *)(ws + w.tot);
-    WVG_HIP(hipMemsetAsync(tot, 0, (size_t)nq * 8, s));
-    uint64_t *part = (uint64_t *)(ws + w.part);
-    {
-        ProfArm arm(ctx);  // wvg_profile_*: the scan dispatch's own events
-        if (arm.rc) return arm.rc;
-        WVG_HIP(launch_scan_bq_emit(a, part, groups, lds, s));
-    }
-    WVG_HIP(launch_emit_prefix(part, nq, (uint32_t)groups, R, (float *)(ws + w.thr), s, 128u * a.nchunks));
+    WVG_HIP(launch_emit_prefix((const uint64_t *)(ws + w.part), nq, (uint32_t)groups, R, (float *)(ws + w.thr), s,
+                               128u * a.nchunks));
     WVG_HIP(launch_emit_filter(a.emit, a.emit_cnt, cap, (const float *)(ws + w.thr), nq, (uint32_t)groups,
-                               BQ_SCAN_WAVES, (uint32_t *)(ws + w.fcnt), tot + nq, s));
+                               BQ_SCAN_WAVES, (uint32_t *)(ws + w.fcnt), tot + nq, s, bound));
     WVG_HIP(launch_emit_gather(a.emit, (const uint32_t *)(ws + w.fcnt), cap, nq, waves, (uint64_t *)(ws + w.out),
                                out_cap, tot, s));
     return WVG_OK;
+}
+
+// The four device steps in one go.
+int run_emit(wvg_ctx *ctx, const ScanArgs &a0, int groups, uint32_t cap, bool lds, uint32_t out_cap, char *ws,
+             const ReplayWs &w, const float *seed, const float *bound, hipStream_t s)
+{
+    ScanArgs a = a0;
+    const int rc = emit_scan(ctx, a, groups, cap, lds, ws, w, seed, s);
+    return rc ? rc : emit_finish(a, groups, cap, out_cap, ws, w, bound, s);
 }
 
 // The heap replay of one query's kept rows (ascending docID): findTopVectorsCached
@@ -460,9 +569,10 @@ void replay_pops(const uint64_t *keys, size_t n, uint32_t R, std::vector<GoItem>
 
 // One query again with buffers that cannot overflow (every row of a wave),
 // seeded with the first pass's thresholds: its own device allocation (this
-// path is for adversarial docID orders only).
-int rerun_full(wvg_ctx *ctx, const ScanArgs &a0, int groups, const float *d_thr_q, hipStream_t s,
-               std::vector<uint64_t> &keys)
+// path is for adversarial docID orders only).  d_bound_q: the query's
+// cross-slab bound on the device, or null.
+int rerun_full(wvg_ctx *ctx, const ScanArgs &a0, int groups, const float *d_thr_q, const float *d_bound_q,
+               hipStream_t s, std::vector<uint64_t> &keys)
 {
     const uint64_t ntiles = a0.tile_end - a0.tile_begin;
     const uint32_t waves = (uint32_t)groups * BQ_SCAN_WAVES;
@@ -487,7 +597,7 @@ int rerun_full(wvg_ctx *ctx, const ScanArgs &a0, int groups, const float *d_thr_
         ScanArgs a = a0;
         a.nq = 1;
         a.cosched = 0;  // same groups, so the same ranges as the first pass
-        rc = run_emit(ctx, a, groups, cap, false, out_cap, ws, w, (const float *)(ws + seed_off), s);
+        rc = run_emit(ctx, a, groups, cap, false, out_cap, ws, w, (const float *)(ws + seed_off), d_bound_q, s);
         if (rc) break;
         uint32_t tot[2] = {0, 0};
         if (hipMemcpyAsync(tot, ws + w.tot, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -530,14 +640,27 @@ size_t replay_workspace_bytes(const wvg_corpus *bq, uint32_t nq, uint32_t R, con
     return replay_ws(nq, (uint32_t)groups, R, e.cap, REPLAY_OUT_CAP).total;
 }
 
-int bq_heap_candidates(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq, uint32_t R,
-                       const uint64_t *d_allow, const SearchPlan &p, char *ws, std::vector<std::vector<GoItem>> &pops)
+#ifdef WVG_TOOLS
+std::atomic<uint64_t> &replay_rerun_count()  // tools build: queries rerun after a per-wave buffer overflowed
 {
-    hipStream_t s = sl->stream;
-    const int groups = replay_groups(bq, nq, p);
-    const EmitPlan e = emit_plan_for(p.te - p.tb, groups, nq, R, bq->ctx->num_cus);
-    const ReplayWs w = replay_ws(nq, (uint32_t)groups, R, e.cap, REPLAY_OUT_CAP);
-    ScanArgs a{};
+    static std::atomic<uint64_t> n{0};
+    return n;
+}
+#endif
+
+int replay_scan(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq, uint32_t R,
+                const uint64_t *d_allow, const SearchPlan &p, char *ws, ReplayPass &rp)
+{
+    rp.groups = replay_groups(bq, nq, p);
+    const EmitPlan e = emit_plan_for(p.te - p.tb, rp.groups, nq, R, bq->ctx->num_cus);
+    rp.cap = e.cap;
+    rp.w = replay_ws(nq, (uint32_t)rp.groups, R, e.cap, REPLAY_OUT_CAP);
+    rp.ws = ws;
+    rp.ctx = bq->ctx;
+    rp.d_qb = d_qb;
+    rp.qpb = qpb;
+    ScanArgs &a = rp.a;
+    a = ScanArgs{};
     a.data = bq->d_data;
     a.valid = bq->d_valid;
     a.allow = d_allow;
@@ -554,13 +677,26 @@ int bq_heap_candidates(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_
     a.nq = nq;
     a.k = R;
     a.cosched = p.cosched;
-    int rc = run_emit(bq->ctx, a, groups, e.cap, e.lds, REPLAY_OUT_CAP, ws, w, nullptr, s);
-    if (rc) return rc;
+    return emit_scan(bq->ctx, a, rp.groups, e.cap, e.lds, ws, rp.w, nullptr, sl->stream);
+}
+
+int replay_filter(const ReplayPass &rp, const float *d_bound, hipStream_t s)
+{
+    return emit_finish(rp.a, rp.groups, rp.cap, REPLAY_OUT_CAP, rp.ws, rp.w, d_bound, s);
+}
+
+int replay_collect(const ReplayPass &rp, StreamSlot *sl, const float *d_bound,
+                   const std::function<void(uint32_t, const uint64_t *, size_t)> &sink)
+{
+    hipStream_t s = sl->stream;
+    const ReplayWs &w = rp.w;
+    char *ws = rp.ws;
+    const uint32_t nq = rp.a.nq;
     // totals, overflow flags and the first REPLAY_HEAD kept rows of every query in one round trip
     const uint32_t head = REPLAY_HEAD;
     const size_t tot_b = (size_t)nq * 8, head_b = (size_t)nq * head * 8;
     Staging st;
-    rc = st.reserve(sl, stage_bytes(tot_b) + stage_bytes(head_b));
+    int rc = st.reserve(sl, stage_bytes(tot_b) + stage_bytes(head_b));
     if (rc) return rc;
     std::vector<char> big(head_b > STAGE_MAX ? head_b : 0);
     char *pin_tot = st.take(tot_b);
@@ -570,16 +706,19 @@ int bq_heap_candidates(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_
                              hipMemcpyDeviceToHost, s));
     WVG_HIP(hipStreamSynchronize(s));
     const uint32_t *tot = (const uint32_t *)pin_tot, *oflow = tot + nq;
-    pops.assign(nq, {});
     std::vector<uint64_t> keys;
     for (uint32_t q = 0; q < nq; q++) {
         const uint64_t *qk = (const uint64_t *)pin_head + (size_t)q * head;
         size_t n = tot[q];
         if (oflow[q] || n > REPLAY_OUT_CAP) {
-            ScanArgs aq = a;
-            aq.queries = (const uint64_t *)d_qb + (size_t)q * qpb;
-            aq.allow = d_allow;  // filtered batches use one shared window (no per-query stride here)
-            rc = rerun_full(bq->ctx, aq, groups, (const float *)(ws + w.thr) + (size_t)q * groups, s, keys);
+#ifdef WVG_TOOLS
+            replay_rerun_count()++;
+#endif
+            ScanArgs aq = rp.a;
+            aq.queries = (const uint64_t *)rp.d_qb + (size_t)q * rp.qpb;
+            // (filtered batches use one shared window: no per-query stride here)
+            rc = rerun_full(rp.ctx, aq, rp.groups, (const float *)(ws + w.thr) + (size_t)q * rp.groups,
+                            d_bound ? d_bound + q : nullptr, s, keys);
             if (rc) return rc;
             qk = keys.data();
             n = keys.size();
@@ -590,9 +729,31 @@ int bq_heap_candidates(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_
             WVG_HIP(hipStreamSynchronize(s));
             qk = keys.data();
         }
-        replay_pops(qk, n, R, pops[q]);
+        sink(q, qk, n);
     }
     return WVG_OK;
+}
+
+void replay_rows(const GoItem *rows, size_t n, uint32_t R, std::vector<GoItem> &pops)
+{
+    GoMaxHeap h(R);
+    for (size_t i = 0; i < n; i++) insert_to_heap(h, R, rows[i].id, rows[i].dist);
+    pops.clear();
+    pops.reserve(h.len());
+    while (h.len()) pops.push_back(h.pop());
+}
+
+int bq_heap_candidates(wvg_corpus *bq, StreamSlot *sl, const void *d_qb, uint32_t qpb, uint32_t nq, uint32_t R,
+                       const uint64_t *d_allow, const SearchPlan &p, char *ws, std::vector<std::vector<GoItem>> &pops)
+{
+    ReplayPass rp;
+    int rc = replay_scan(bq, sl, d_qb, qpb, nq, R, d_allow, p, ws, rp);
+    if (rc) return rc;
+    rc = replay_filter(rp, nullptr, sl->stream);
+    if (rc) return rc;
+    pops.assign(nq, {});
+    return replay_collect(rp, sl, nullptr,
+                          [&](uint32_t q, const uint64_t *keys, size_t n) { replay_pops(keys, n, R, pops[q]); });
 }
 
 int bq_rescore_replay(wvg_corpus *bq, wvg_corpus *f32, const float *queries, uint32_t nq, uint32_t k, uint32_t R,

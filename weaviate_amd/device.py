@@ -319,7 +319,9 @@ class Multi:
 
 class MultiCorpus:
     """wvg_multi_corpus_*: docIDs dealt to the devices in contiguous slabs;
-    search = every slab's scan on its device, one RCCL all-gather, the merge."""
+    search = every slab's scan on its device, one RCCL all-gather, the merge.
+    The exact BQ flow over a BQ (+ F32) multi corpus: multi_search_bq_rescore /
+    multi_search_bq_candidates below."""
 
     def __init__(self, multi: Multi, kind: int, metric: int, dim: int, rows: int):
         self.multi, self.lib = multi, multi.lib
@@ -369,3 +371,36 @@ class MultiCorpus:
         check(self.lib.wvg_multi_search(self.handle, fptr(q), nq, k, u64ptr(aw) if aw is not None else None, an,
                                         u64ptr(ids), fptr(dists), u32ptr(counts)))
         return ids, dists, counts
+
+
+def multi_search_bq_candidates(bq: MultiCorpus, queries, rescore_limit: int, allow=None):
+    """wvg_multi_search_bq_candidates: search_bq_candidates over a BQ multi corpus
+    (one heap of rescore_limit over all slabs; ids are global docIDs)."""
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    if q.ndim == 1:
+        q = q[None, :]
+    nq, R = q.shape[0], rescore_limit
+    ids = np.empty((nq, R), dtype=np.uint64)
+    dists = np.empty((nq, R), dtype=np.float32)
+    counts = np.empty(nq, dtype=np.uint32)
+    aw, an = (None, 0) if allow is None else (np.ascontiguousarray(allow, dtype=np.uint64), len(allow))
+    check(bq.lib.wvg_multi_search_bq_candidates(bq.handle, fptr(q), nq, R, u64ptr(aw) if aw is not None else None,
+                                                an, u64ptr(ids), fptr(dists), u32ptr(counts)))
+    return ids, dists, counts
+
+
+def multi_search_bq_rescore(bq: MultiCorpus, f32: MultiCorpus, queries, k: int, rescore_limit: int, allow=None):
+    """wvg_multi_search_bq_rescore: search_bq_rescore over a BQ and an F32 multi
+    corpus of the same Multi (flat.searchByVectorBQ, V/flat/index.go:347-389)."""
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    if q.ndim == 1:
+        q = q[None, :]
+    nq = q.shape[0]
+    ids = np.empty((nq, k), dtype=np.uint64)
+    dists = np.empty((nq, k), dtype=np.float32)
+    counts = np.empty(nq, dtype=np.uint32)
+    aw, an = (None, 0) if allow is None else (np.ascontiguousarray(allow, dtype=np.uint64), len(allow))
+    check(bq.lib.wvg_multi_search_bq_rescore(bq.handle, f32.handle, fptr(q), nq, k, rescore_limit,
+                                             u64ptr(aw) if aw is not None else None, an,
+                                             u64ptr(ids), fptr(dists), u32ptr(counts)))
+    return ids, dists, counts

@@ -280,3 +280,34 @@ class FlatIndex:
             if max_limit >= 0 and total > max_limit:
                 break
         return np.asarray(res_ids, dtype=np.uint64), np.asarray(res_d, dtype=np.float32)
+
+
+def multi_bq_kept_rows(dists, valid, R: int, slab: int, range_rows: int):
+    """Rule R of the multi-GPU BQ flow (wvg_multi_search_bq_*),
+    restated: which rows the slabs hand to the host heap.
+
+    The heap of R over docIDs in ascending order inserts row i iff fewer than
+    R live allowed rows precede it or d_i < T_i, T_i the R-th smallest distance
+    of all earlier live allowed rows.  A row of slab s (docIDs [s * slab, (s +
+    1) * slab)), range g (range_rows consecutive rows of the slab) is kept iff
+    d_i < min(thr[g], X_s): thr[g] the R-th smallest distance of the slab's
+    live allowed rows before range g, X_s that of all live allowed rows of
+    slabs 0..s-1, each +inf while fewer than R such rows exist.  Both are upper
+    bounds of T_i, so the kept rows are a superset of the inserted ones and
+    replaying them in docID order reproduces the heap.  Returns a bool mask.
+    """
+    d = np.asarray(dists, dtype=np.float32)
+    live = np.ones(len(d), bool) if valid is None else np.asarray(valid).astype(bool)
+    keep = np.zeros(len(d), bool)
+
+    def rth(values):  # the R-th smallest, +inf below R values
+        return np.partition(values, R - 1)[R - 1] if len(values) >= R else np.float32(np.inf)
+
+    for s0 in range(0, len(d), slab):
+        s1 = min(s0 + slab, len(d))
+        x_s = rth(d[:s0][live[:s0]])
+        for g0 in range(s0, s1, range_rows):
+            g1 = min(g0 + range_rows, s1)
+            thr = rth(d[s0:g0][live[s0:g0]])
+            keep[g0:g1] = live[g0:g1] & (d[g0:g1] < min(thr, x_s))
+    return keep

@@ -573,6 +573,95 @@ func (x *Corpus) SearchBatch(qs []float32, nq, k int, allow helpers.AllowList) (
 	return r, nil
 }
 
+// SearchGroup: one flat.SearchByVector per (corpus, query) pair -- query i (qs is
+// len(corpora)*dims floats) against corpora[i], the tenants of a multi-tenant
+// class, where every query names exactly one shard (adapters/repos/db/index.go:
+// 1516-1539) -- as one scan launch and one merge launch (wvg_search_group).  The
+// corpora are F32 corpora of one context, metric and dims; one may appear several
+// times.  allows is empty (no query filtered) or holds one list per query: nil
+// means no filter for that query, a non-nil empty list an empty result for that
+// query alone (V/flat/index.go:423-427) -- the others are searched as usual.
+// A package-level function, not a method: it takes one AllowList per query, not
+// one per call.
+func SearchGroup(corpora []*Corpus, qs []float32, k int, allows []helpers.AllowList) (*Results, error) {
+	nq := len(corpora)
+	r := emptyResults(nq, k)
+	if nq == 0 || k == 0 {
+		return r, nil
+	}
+	if corpora[0] == nil {
+		return nil, errors.New("nil corpus")
+	}
+	dims := corpora[0].dims
+	if len(qs) != len(corpora)*dims {
+		return nil, errors.New("vector lengths don't match")
+	}
+	if len(allows) != 0 && len(allows) != len(corpora) {
+		return nil, errors.New("allow lists don't match the corpora")
+	}
+	keep := make([]interface{}, 0, nq)
+	hs := make([]*C.wvg_corpus, nq)
+	for i, x := range corpora {
+		if x == nil {
+			return nil, fmt.Errorf("corpora[%d] is nil", i)
+		}
+		hs[i] = x.h
+		keep = append(keep, x)
+	}
+	defer pin(keep...)()
+	// The per-query bitmaps go through one C allocation: the pointer table handed
+	// to the library may not hold Go pointers.  A non-nil empty list is a non-NULL
+	// pointer with zero words.
+	var ap []*C.uint64_t
+	var aw []uint64
+	if len(allows) != 0 {
+		bitmaps := make([][]uint64, nq)
+		total := 1
+		for i, a := range allows {
+			if a == nil || a.IsEmpty() {
+				continue
+			}
+			bitmaps[i] = make([]uint64, a.Max()/64+1)
+			it := a.Iterator()
+			for id, more := it.Next(); more; id, more = it.Next() {
+				bitmaps[i][id/64] |= 1 << (id % 64)
+			}
+			total += len(bitmaps[i])
+		}
+		block := C.calloc(C.size_t(total), 8)
+		if block == nil {
+			return nil, errors.New("out of memory")
+		}
+		defer C.free(block)
+		words := unsafe.Slice((*uint64)(block), total)
+		ap = make([]*C.uint64_t, nq)
+		aw = make([]uint64, nq)
+		at := 1 // word 0: the target of the empty lists' pointers
+		for i, a := range allows {
+			if a == nil {
+				continue
+			}
+			if bitmaps[i] == nil {
+				ap[i] = (*C.uint64_t)(block)
+				continue
+			}
+			copy(words[at:], bitmaps[i])
+			ap[i] = (*C.uint64_t)(unsafe.Pointer(&words[at]))
+			aw[i] = uint64(len(bitmaps[i]))
+			at += len(bitmaps[i])
+		}
+	}
+	var app **C.uint64_t
+	if ap != nil {
+		app = &ap[0]
+	}
+	if e := err(C.wvg_search_group(&hs[0], f32p(qs), C.uint32_t(nq), C.uint32_t(k), app, u64p(aw),
+		u64p(r.IDs), f32p(r.Dists), u32p(r.Counts))); e != nil {
+		return nil, e
+	}
+	return r, nil
+}
+
 // SearchBQRescore: flat.searchByVectorBQ (V/flat/index.go:347-389) with the
 // float rows resident in f32 (same dims / idBase / metric as x).
 func (x *Corpus) SearchBQRescore(f32 *Corpus, qs []float32, nq, k, rescoreLimit int,

@@ -222,6 +222,20 @@ int wvg_pq_set_codebook(wvg_corpus *c, const float *centers, uint32_t m, uint32_
 int wvg_search(wvg_corpus *c, const float *queries, uint32_t nq, uint32_t k,
                const uint64_t *allow_bits, uint64_t allow_words, uint64_t *out_ids,
                float *out_dists, uint32_t *out_counts);
+/* nq flat.SearchByVector calls (V/flat/index.go:307-334), query i against
+ * corpora[i] -- the shards of a multi-tenant class, one tenant per query
+ * (adapters/repos/db/index.go:1516-1539, 1554-1565) -- in ONE scan launch and
+ * one merge launch.  All corpora: kind F32, one context, one metric, one dim
+ * (a class's tenants share its vector index config); a corpus may appear any
+ * number of times.  queries [nq][dim].  allow_bits: NULL (no query filtered)
+ * or nq pointers, entry i NULL or a bitmap over corpora[i]'s global docIDs of
+ * allow_words[i] words (non-NULL with 0 words, or no allowed id in the
+ * corpus: empty result for that query, as wvg_search).  k <= 256.
+ * Outputs [nq][k] / counts[nq] exactly as nq wvg_search(corpora[i], q_i, 1, k,
+ * allow_i) calls would write them: ids, distance bits, counts, padding.     */
+int wvg_search_group(wvg_corpus *const *corpora, const float *queries, uint32_t nq, uint32_t k,
+                     const uint64_t *const *allow_bits, const uint64_t *allow_words,
+                     uint64_t *out_ids, float *out_dists, uint32_t *out_counts);
 /* flat.searchByVectorBQ (V/flat/index.go:347-389): Hamming top-R over `bq`,
  * R = max(rescore_limit, k) (index.go:297-305), exact rescore of the R
  * candidates against the device-resident float rows of `f32`, top-k.      */

@@ -77,6 +77,8 @@ SIGNATURES = {
     "wvg_pq_set_codebook": (c_int, [c_void_p, _P(c_float), c_uint32, c_uint32]),
     "wvg_search": (c_int, [c_void_p, _P(c_float), c_uint32, c_uint32, _P(c_uint64), c_uint64,
                            _P(c_uint64), _P(c_float), _P(c_uint32)]),
+    "wvg_search_group": (c_int, [_P(c_void_p), _P(c_float), c_uint32, c_uint32, _P(c_void_p), _P(c_uint64),
+                                 _P(c_uint64), _P(c_float), _P(c_uint32)]),
     "wvg_search_bq_rescore": (c_int, [c_void_p, c_void_p, _P(c_float), c_uint32, c_uint32, c_uint32,
                                       _P(c_uint64), c_uint64, _P(c_uint64), _P(c_float), _P(c_uint32)]),
     "wvg_search_bq_candidates": (c_int, [c_void_p, _P(c_float), c_uint32, c_uint32, _P(c_uint64), c_uint64,

@@ -357,6 +357,42 @@ bool qshare_supported(int metric, uint32_t dim, int order512);
 uint32_t qshare_queries_per_pass(uint32_t dim, uint32_t k);
 uint32_t qshare_groups(uint64_t ntiles, int num_cus);
 hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s);
+// Grouped search (wvg_search_group, wvg_group.hip): nq single-query scans, query i
+// over a corpus of its own, as ONE scan launch and one merge launch.  The host
+// writes a descriptor per query and a work-item table; workgroup b of the scan
+// takes items[b] -- a run of tiles of one query's corpus -- and leaves one
+// k-list at partials[(list0 + range) * k]; merge workgroup q merges query q's
+// nlists lists.  The hand-off between the two launches is stream order.
+struct GroupQuery {
+    const void *data;        // the query's corpus: tiled rows
+    const uint64_t *valid;   // one word per tile
+    uint64_t id_base;
+    uint64_t tile_begin, tile_end;  // tiles that can hold a live, allowed row
+    uint64_t allow_off;      // the query's window: word offset into the call's allow block,
+    uint64_t allow_words;    // its length in words (tiles) and the tile of its word 0
+    uint64_t allow_t0;
+    uint32_t list0, nlists;  // the query's lists in `partials` (nlists = 0: nothing live or allowed)
+    uint32_t filtered, pad;  // 1: the allow window applies
+};
+static_assert(sizeof(GroupQuery) == 80, "descriptor layout shared by host and device");
+struct GroupItem {
+    uint32_t query, range;   // range: the item's index among its query's lists
+    uint32_t t0, t1;         // its tiles [t0, t1)
+};
+struct GroupArgs {
+    const GroupQuery *desc;  // [nq]
+    const GroupItem *items;  // [gridDim.x]
+    const float *queries;    // [nq][qpitch], prepared (normalized for cosine)
+    const uint64_t *allow;   // the call's allow windows, back to back
+    uint64_t *partials;      // [lists][k]
+    uint32_t qpitch, k, dim, nchunks;
+    int metric, order512;
+};
+hipError_t launch_scan_f32_group(const GroupArgs &a, uint32_t nitems, hipStream_t s);
+hipError_t launch_merge_group(const GroupQuery *desc, const uint64_t *partials, uint32_t nq, uint32_t k, uint64_t *ids,
+                              float *dists, uint32_t *counts, hipStream_t s);
+// Tiles per work item (the item rule, DESIGN.md section 5 "Grouped search over tenants").
+uint32_t group_item_tiles(uint64_t total_tiles, int num_cus);
 // ids KEY_NONE, dists +inf, counts 0 for nq queries (empty corpus / slab).
 hipError_t launch_fill_empty(uint64_t *ids, float *dists, uint32_t *counts, uint32_t nq, uint32_t k, hipStream_t s);
 hipError_t launch_scan_bq(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s);

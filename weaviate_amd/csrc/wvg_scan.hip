@@ -63,46 +63,6 @@ __device__ __forceinline__ void wave_range(const ScanArgs &a, int waves_per_grou
     t1 = a.tile_begin + ntiles * (gw + 1) / total;
 }
 
-// Phase-2 merge body for one query (see merge_keys_kernel): WAVES waves read
-// `nlists` ascending lists transposed, then tree-merge in LDS; wave 0 writes.
-// rec (host-read results, see StreamJob::records): entry i goes to rec[i] as ONE
-// 16-byte store {id lo, id hi, dist bits, tag}, then the header {count, tag}
-// at rec[k] -- the host accepts only entries carrying its call's tag.
-template <int E, int WAVES>
-__device__ __forceinline__ void merge_lists_body(const uint64_t *src, uint32_t nlists, uint32_t list_len, uint32_t k,
-                                                 uint64_t id_base, uint64_t *ids, float *dists, uint32_t *count,
-                                                 uint4 *rec = nullptr, uint32_t tag = 0, bool sys_release = false)
-{
-    const int lane = threadIdx.x & 63, wave = wave_id();
-    WaveTopK<E> tk;
-    tk.init((int)k);
-    for (uint32_t g0 = (uint32_t)wave * 64; g0 < nlists; g0 += WAVES * 64) {
-        const uint32_t list = g0 + lane;
-        const uint64_t *lp = src + (size_t)list * list_len;
-        // four entries per lane in flight at a time (independent loads): a one-query
-        // merge sits on the launch's critical path, where one dependent load per entry
-        // (~1 us each from L2) was most of its time
-        bool done = false;
-        for (uint32_t r0 = 0; r0 < list_len && !done; r0 += 4) {
-            uint64_t c4[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                c4[i] = (r0 + i < list_len && list < nlists) ? lp[r0 + i] : WVG_KEY_NONE;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const uint32_t r = r0 + (uint32_t)i;
-                if (r >= list_len) break;
-                if (list_len > 1 && r > 0 && __ballot(c4[i] < tk.tau) == 0ull) {  // sorted lists: done
-                    done = true;
-                    break;
-                }
-                tk.offer(c4[i]);
-            }
-        }
-    }
-    merge_finish<E, WAVES>(tk, k, id_base, ids, dists, count, rec, tag, sys_release);
-}
-
 // One wave's tiles [t0, t1) for one query: one tile's loads in flight per
 // wave; tiles with no live/allowed row are skipped without touching their rows.
 // rev: walk the range downwards (t1-1 .. t0); the result does not depend on
@@ -731,7 +691,6 @@ hipError_t launch_scan_f32(const ScanArgs &a, uint64_t *partials, int groups, hi
 // the first batch with no key below the threshold ends the group (every later
 // key of those lists is larger).  Unsorted input: list_len = 1.
 // ---------------------------------------------------------------------------
-constexpr int MERGE_WAVES = 8;
 
 template <int E>
 __global__ __launch_bounds__(MERGE_WAVES * 64) void merge_keys_kernel(const uint64_t *partials, uint32_t nlists,

@@ -254,6 +254,47 @@ class Corpus:
         return ids[:cnt.value], dists[:cnt.value]
 
 
+def search_group(corpora, queries, k: int, allows=None):
+    """wvg_search_group: query i against corpora[i] (the tenants of one class: F32,
+    one context, one metric, one dim), all in one scan launch and one merge launch.
+    allows: None, or one entry per query -- None (no filter) or a bitmap over that
+    corpus's global docIDs (allow_bitmap; an empty array allows nothing).  Returns
+    (ids [nq][k], dists [nq][k], counts [nq]), as nq Corpus.search calls would."""
+    corpora = list(corpora)
+    nq = len(corpora)
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    if q.ndim == 1:
+        q = q[None, :]
+    if q.shape[0] != nq:
+        raise ValueError(f"{q.shape[0]} queries for {nq} corpora")
+    if allows is not None and len(allows) != nq:
+        raise ValueError(f"{len(allows)} allow lists for {nq} corpora")
+    lib = _lib.load()
+    handles = (c_void_p * max(nq, 1))(*[c.handle if c is not None else None for c in corpora])
+    ids = np.empty((nq, k), dtype=np.uint64)
+    dists = np.empty((nq, k), dtype=np.float32)
+    counts = np.empty(nq, dtype=np.uint32)
+    ap = aw = None
+    keep = []  # the bitmaps, alive through the call
+    if allows is not None:
+        ap = (c_void_p * max(nq, 1))()
+        aw = np.zeros(max(nq, 1), dtype=np.uint64)
+        for i, a in enumerate(allows):
+            if a is None:
+                continue
+            words = np.ascontiguousarray(a, dtype=np.uint64)
+            if words.size == 0:  # non-NULL with 0 words: nothing allowed
+                words = np.zeros(1, dtype=np.uint64)
+                aw[i] = 0
+            else:
+                aw[i] = words.size
+            keep.append(words)
+            ap[i] = words.ctypes.data
+    check(lib.wvg_search_group(handles, fptr(q), nq, k, ap, u64ptr(aw) if aw is not None else None,
+                               u64ptr(ids), fptr(dists), u32ptr(counts)))
+    return ids, dists, counts
+
+
 def search_bq_candidates(bq: Corpus, queries, rescore_limit: int, allow=None):
     """wvg_search_bq_candidates: findTopVectorsCached's heap of rescore_limit and
     its pop order (V/flat/index.go:355-374): (ids [nq][R], dists [nq][R], counts)."""

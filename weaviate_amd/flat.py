@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import KIND_BQ, KIND_F32, METRIC_BY_NAME, WVG_ERR_DIM_MISMATCH, WvgError
-from .device import Corpus, allow_bitmap, search_bq_rescore
+from .device import Corpus, allow_bitmap, search_bq_rescore, search_group
 from .distancer import provider_for
 
 DEFAULT_SEARCH_BY_DIST_INITIAL_LIMIT = 100  # V/common/search_by_dist_params.go:17
@@ -280,6 +280,30 @@ class FlatIndex:
             if max_limit >= 0 and total > max_limit:
                 break
         return np.asarray(res_ids, dtype=np.uint64), np.asarray(res_d, dtype=np.float32)
+
+
+def SearchByVectorGroup(indexes, vectors, k: int, allows=None):
+    """One SearchByVector per (index, vector) pair -- the tenants of a multi-tenant
+    class, whose queries each name one shard (adapters/repos/db/index.go:1516-1539) --
+    as one grouped device call (wvg_search_group).  indexes: uncompressed FlatIndex
+    objects of one context, distance and dims; allows: None or one AllowList / None
+    per query (an empty list: no results for that query, as SearchByVector).  Returns
+    [(ids, dists)] per query, trimmed to its result count."""
+    indexes = list(indexes)
+    if k < 0:
+        raise ValueError("k must be >= 0")
+    for ix in indexes:
+        if ix.bq is not None:
+            raise ValueError("SearchByVectorGroup: compressed flat indexes are searched one by one")
+    if allows is not None and len(allows) != len(indexes):
+        raise ValueError("indexes and allows sizes does not match")
+    bms = None
+    if allows is not None:
+        bms = [None if a is None else (np.empty(0, dtype=np.uint64) if a.IsEmpty() else a.bitmap()) for a in allows]
+    if not indexes:
+        return []
+    ids, dists, counts = search_group([ix.vectors for ix in indexes], vectors, k, bms)
+    return [(ids[i, :int(counts[i])], dists[i, :int(counts[i])]) for i in range(len(indexes))]
 
 
 def multi_bq_kept_rows(dists, valid, R: int, slab: int, range_rows: int):

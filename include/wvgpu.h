@@ -206,7 +206,12 @@ int wvg_corpus_get_batch(wvg_corpus *c, const uint64_t *ids, uint64_t n, void *o
  * distribution 0 = uniform [-1,1), 1 = integers 0..255.  F32 and BQ only.  */
 int wvg_corpus_fill_synthetic(wvg_corpus *c, uint64_t seed, uint64_t n, int distribution);
 /* PQ codebook: centers [m][ks][dim/m] float32 (KMeans centers, CH/kmeans.go:85-93).
- * Validation as NewProductQuantizer (CH/product_quantization.go:187-197).  */
+ * Validation as NewProductQuantizer (CH/product_quantization.go:187-197).
+ * Every accepted shape (m a divisor of dim, ks <= 256) is searchable: the
+ * scan keeps the query's m x ks fp32 lookup table in LDS while it fits beside
+ * its top-k buffer (at ks = 256: m <= 152 for k <= 64, m <= 144 for k <= 128,
+ * m <= 128 for k <= 256, and any m that fits 160 KiB above k = 256) and reads
+ * it in global memory above that -- the same distances, bit for bit.      */
 int wvg_pq_set_codebook(wvg_corpus *c, const float *centers, uint32_t m, uint32_t ks);
 
 /* ---- search ---------------------------------------------------------------
@@ -218,7 +223,8 @@ int wvg_pq_set_codebook(wvg_corpus *c, const float *centers, uint32_t m, uint32_
  * word i/64; an empty allow list yields empty results (index.go:425-427).
  * Outputs: [nq][k] ids/dists, counts[nq] = min(k, live allowed rows).
  * Any k: up to 256 the fused register top-k of the scan; above, a radix
- * select + sort over per-row distance keys in HBM (the same distances).    */
+ * select + sort over per-row distance keys in HBM (the same distances).
+ * PQ: any (m, ks) of wvg_pq_set_codebook, wherever the lookup table lives.  */
 int wvg_search(wvg_corpus *c, const float *queries, uint32_t nq, uint32_t k,
                const uint64_t *allow_bits, uint64_t allow_words, uint64_t *out_ids,
                float *out_dists, uint32_t *out_counts);

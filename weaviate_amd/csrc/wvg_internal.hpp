@@ -607,6 +607,23 @@ inline void launch_timed(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32
         hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
     }
 }
+// Does a launch of Kern with `dynamic` bytes of dynamic LDS fit one workgroup's
+// LDS (160 KiB on gfx950)?  Counts the kernel's static LDS as the code object
+// states it; a kernel whose attributes cannot be read never fits.
+constexpr size_t WVG_LDS_BYTES = 160 * 1024;
+template <auto Kern>
+inline bool fits_lds(size_t dynamic)
+{
+    static const size_t fixed = [] {
+        hipFuncAttributes fa{};
+        if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(Kern)) != hipSuccess) {
+            (void)hipGetLastError();  // the caller's launch check must not see this one
+            return WVG_LDS_BYTES + 1;
+        }
+        return (size_t)fa.sharedSizeBytes;
+    }();
+    return fixed + dynamic <= WVG_LDS_BYTES;
+}
 // Phase 2: per query `nlists` ascending lists of `list_len` keys -> final
 // (ids = id_base + slot, dists, counts).
 hipError_t launch_merge_lists(const uint64_t *partials, uint32_t nq, uint32_t nlists, uint32_t list_len, uint32_t k,

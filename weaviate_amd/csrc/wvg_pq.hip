@@ -501,17 +501,23 @@ __device__ __forceinline__ uint64_t pq_tile_mask(const ScanArgs &a, uint64_t t)
 // (CH/product_quantization.go:85-104).  Fixed M: the next live tile's codes are
 // loaded (non-temporal) while the current tile is looked up, so the HBM
 // latency is covered by 16 waves x 2 tiles in flight per CU.
-template <int E, int M, int KS>
+// GL (generic form only): the LUT does not fit in LDS beside the workgroup
+// top-k buffer (launch_pq_k8), so every lookup reads the query's LUT in global
+// memory -- no staging, no LDS request; the sums are the same.
+template <int E, int M, int KS, bool GL = false>
 __global__ __launch_bounds__(PQ_SCAN_WAVES * 64) void scan_pq_kernel(ScanArgs a, uint64_t *partials)
 {
+    static_assert(!GL || (M == 0 && KS == 0), "the global-LUT form is the generic kernel's");
     extern __shared__ __attribute__((aligned(16))) float lut[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t qi = blockIdx.y;
     const uint32_t m = M > 0 ? (uint32_t)M : a.pq_m;
     const uint32_t ks = KS > 0 ? (uint32_t)KS : a.pq_ks;
     const float *glut = reinterpret_cast<const float *>(a.queries) + (size_t)qi * a.qpitch;
-    for (uint32_t i = threadIdx.x; i < m * ks; i += blockDim.x) lut[i] = glut[i];
-    __syncthreads();
+    if constexpr (!GL) {
+        for (uint32_t i = threadIdx.x; i < m * ks; i += blockDim.x) lut[i] = glut[i];
+        __syncthreads();
+    }
     const uint4 *data = reinterpret_cast<const uint4 *>(a.data);
     const uint32_t nch = a.nchunks;
     const uint64_t ntiles = a.tile_end - a.tile_begin;
@@ -573,7 +579,9 @@ __global__ __launch_bounds__(PQ_SCAN_WAVES * 64) void scan_pq_kernel(ScanArgs a,
             const uint64_t msk = pq_tile_mask(a, t);
             if (msk == 0ull) continue;
             const uint4 *rp = data + (size_t)t * nch * 64 + lane;
-            const float dist = wrap_metric(a.metric, pq_row_sum(rp, nch, m, ks, lut, (uint64_t)lane));
+            const float sum = GL ? pq_row_sum(rp, nch, m, ks, glut, (uint64_t)lane)
+                                 : pq_row_sum(rp, nch, m, ks, lut, (uint64_t)lane);
+            const float dist = wrap_metric(a.metric, sum);
             tk.offer(((msk >> lane) & 1ull) ? wvg_make_key(dist, (uint32_t)(t * 64 + lane)) : WVG_KEY_NONE);
         }
     }
@@ -1506,6 +1514,38 @@ static bool launch_pq_wide(const ScanArgs &a, uint64_t *partials, int groups, hi
     return true;
 }
 
+// K8 for any (m, ks).  The m x ks fp32 LUT goes to dynamic LDS where it fits
+// beside the instantiation's own static LDS (the workgroup top-k buffer of
+// group_combine_store: 8 / 16 / 32 KiB for E = 1 / 2 / 4) -- at ks = 256 that
+// is m <= 152 / 144 / 128; above it the generic kernel reads the LUT in
+// global memory.  The fixed-M forms (m <= 64) always fit.
+template <int E, int M, int KS>
+static bool launch_pq_k8_lds(const ScanArgs &a, uint64_t *partials, dim3 grid, dim3 block, hipStream_t s)
+{
+    const size_t lds = (size_t)a.pq_m * a.pq_ks * 4;
+    if (!fits_lds<&scan_pq_kernel<E, M, KS>>(lds)) return false;
+    launch_timed((scan_pq_kernel<E, M, KS>), grid, block, (uint32_t)lds, s, a, partials);
+    return true;
+}
+
+template <int E>
+static hipError_t launch_pq_k8(const ScanArgs &a, uint64_t *partials, dim3 grid, dim3 block, hipStream_t s)
+{
+    bool done = false;
+    if (a.pq_ks == 256) {
+        switch (a.pq_m) {
+        case 8: done = launch_pq_k8_lds<E, 8, 256>(a, partials, grid, block, s); break;
+        case 16: done = launch_pq_k8_lds<E, 16, 256>(a, partials, grid, block, s); break;
+        case 32: done = launch_pq_k8_lds<E, 32, 256>(a, partials, grid, block, s); break;
+        case 64: done = launch_pq_k8_lds<E, 64, 256>(a, partials, grid, block, s); break;
+        default: break;
+        }
+    }
+    if (!done && !launch_pq_k8_lds<E, 0, 0>(a, partials, grid, block, s))
+        launch_timed((scan_pq_kernel<E, 0, 0, true>), grid, block, 0, s, a, partials);
+    return hipGetLastError();
+}
+
 template <int E>
 static hipError_t launch_pq_e(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s);
 
@@ -1648,17 +1688,7 @@ static hipError_t launch_pq_e_variant(const ScanArgs &a, uint64_t *partials, int
         }
         return hipGetLastError();
     }
-    if (a.pq_ks == 256) {
-        switch (a.pq_m) {
-        case 8: launch_timed((scan_pq_kernel<E, 8, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        case 16: launch_timed((scan_pq_kernel<E, 16, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        case 32: launch_timed((scan_pq_kernel<E, 32, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        case 64: launch_timed((scan_pq_kernel<E, 64, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        default: break;
-        }
-    }
-    launch_timed((scan_pq_kernel<E, 0, 0>), grid, block, lds, s, a, partials);
-    return hipGetLastError();
+    return launch_pq_k8<E>(a, partials, grid, block, s);
 }
 #endif  // WVG_TOOLS
 
@@ -1668,7 +1698,7 @@ static hipError_t launch_pq_e_variant(const ScanArgs &a, uint64_t *partials, int
 //   - a dense corpus (>= 3/4 of the slots live, no allow list): K8e, 8 waves;
 //   - otherwise (allow lists, many deletes -- dead tiles are skipped), and
 //     wherever K8e's compile-time LDS layout check fails: K8b;
-// any other (m, ks): K8, the LUT in LDS in segment order.
+// any other (m, ks): K8 (launch_pq_k8), the LUT in segment order, in LDS where it fits.
 template <int E>
 static hipError_t launch_pq_e(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s)
 {
@@ -1687,22 +1717,11 @@ static hipError_t launch_pq_e(const ScanArgs &a, uint64_t *partials, int groups,
         launch_timed((scan_pq32_rot_kernel<E, 6, false, 16>), grid, block, 4 * lds, s, a, partials);
         return hipGetLastError();
     }
-    if (a.pq_ks == 256) {
-        switch (a.pq_m) {
-        case 8: launch_timed((scan_pq_kernel<E, 8, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        case 16: launch_timed((scan_pq_kernel<E, 16, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        case 32: launch_timed((scan_pq_kernel<E, 32, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        case 64: launch_timed((scan_pq_kernel<E, 64, 256>), grid, block, lds, s, a, partials); return hipGetLastError();
-        default: break;
-        }
-    }
-    launch_timed((scan_pq_kernel<E, 0, 0>), grid, block, lds, s, a, partials);
-    return hipGetLastError();
+    return launch_pq_k8<E>(a, partials, grid, block, s);
 }
 
 hipError_t launch_scan_pq(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s)
 {
-    if ((size_t)a.pq_m * a.pq_ks * 4 > 160 * 1024) return hipErrorInvalidValue;
     if (a.k <= 64) return launch_pq_e<1>(a, partials, groups, s);
     if (a.k <= 128) return launch_pq_e<2>(a, partials, groups, s);
     return launch_pq_e<4>(a, partials, groups, s);

@@ -90,14 +90,18 @@ __global__ __launch_bounds__(256) void ordkeys_bq_kernel(ScanArgs a, uint32_t *k
     }
 }
 
-// S1, PQ: ADC with the query's LUT in LDS (CH/product_quantization.go:85-104), as K8.
+// S1, PQ: ADC with the query's LUT in LDS (CH/product_quantization.go:85-104), as K8;
+// GL: a LUT larger than the LDS is read in global memory instead (same sums).
+template <bool GL>
 __global__ __launch_bounds__(256) void ordkeys_pq_kernel(ScanArgs a, uint32_t *keys)
 {
-    extern __shared__ float lut[];
+    extern __shared__ float lds_lut[];
     const uint32_t m = a.pq_m, ks = a.pq_ks;
     const float *glut = reinterpret_cast<const float *>(a.queries);
-    for (uint32_t i = threadIdx.x; i < m * ks; i += blockDim.x) lut[i] = glut[i];
-    __syncthreads();
+    if constexpr (!GL) {
+        for (uint32_t i = threadIdx.x; i < m * ks; i += blockDim.x) lds_lut[i] = glut[i];
+        __syncthreads();
+    }
     const int lane = threadIdx.x & 63;
     const uint64_t ntiles = a.tile_end - a.tile_begin;
     const uint64_t gw = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(256) void ordkeys_pq_kernel(ScanArgs a, uint32_t *k
         uint32_t key = ORD_NONE;
         if ((msk >> lane) & 1ull) {
             const uint4 *rp = data + (size_t)t * a.nchunks * 64 + lane;
-            const float sum = pq_row_sum(rp, a.nchunks, m, ks, lut, (uint64_t)lane);
+            const float sum = pq_row_sum(rp, a.nchunks, m, ks, GL ? glut : lds_lut, (uint64_t)lane);
             key = wvg_ord_f32(wrap_metric(a.metric, sum));
         }
         keys[i * 64 + lane] = key;
@@ -134,7 +138,11 @@ hipError_t launch_ordkeys(const ScanArgs &a, int kind, int num_cus, uint32_t *ke
     } else if (kind == WVG_KIND_BQ) {
         hipLaunchKernelGGL(ordkeys_bq_kernel, grid, block, 0, s, a, keys);
     } else {
-        hipLaunchKernelGGL(ordkeys_pq_kernel, grid, block, (size_t)a.pq_m * a.pq_ks * 4, s, a, keys);
+        const size_t lds = (size_t)a.pq_m * a.pq_ks * 4;
+        if (fits_lds<&ordkeys_pq_kernel<false>>(lds))
+            hipLaunchKernelGGL(ordkeys_pq_kernel<false>, grid, block, lds, s, a, keys);
+        else
+            hipLaunchKernelGGL(ordkeys_pq_kernel<true>, grid, block, 0, s, a, keys);
     }
     return hipGetLastError();
 }

@@ -609,54 +609,167 @@ func SearchGroup(corpora []*Corpus, qs []float32, k int, allows []helpers.AllowL
 		keep = append(keep, x)
 	}
 	defer pin(keep...)()
-	// The per-query bitmaps go through one C allocation: the pointer table handed
-	// to the library may not hold Go pointers.  A non-nil empty list is a non-NULL
-	// pointer with zero words.
-	var ap []*C.uint64_t
+	// The per-query bitmaps go through one C allocation (groupAllows).
+	var app **C.uint64_t
 	var aw []uint64
 	if len(allows) != 0 {
-		bitmaps := make([][]uint64, nq)
-		total := 1
-		for i, a := range allows {
-			if a == nil || a.IsEmpty() {
-				continue
-			}
-			bitmaps[i] = make([]uint64, a.Max()/64+1)
-			it := a.Iterator()
-			for id, more := it.Next(); more; id, more = it.Next() {
-				bitmaps[i][id/64] |= 1 << (id % 64)
-			}
-			total += len(bitmaps[i])
+		ap, w, free, e := groupAllows(allows, nq)
+		if e != nil {
+			return nil, e
 		}
-		block := C.calloc(C.size_t(total), 8)
-		if block == nil {
-			return nil, errors.New("out of memory")
-		}
-		defer C.free(block)
-		words := unsafe.Slice((*uint64)(block), total)
-		ap = make([]*C.uint64_t, nq)
-		aw = make([]uint64, nq)
-		at := 1 // word 0: the target of the empty lists' pointers
-		for i, a := range allows {
-			if a == nil {
-				continue
-			}
-			if bitmaps[i] == nil {
-				ap[i] = (*C.uint64_t)(block)
-				continue
-			}
-			copy(words[at:], bitmaps[i])
-			ap[i] = (*C.uint64_t)(unsafe.Pointer(&words[at]))
-			aw[i] = uint64(len(bitmaps[i]))
-			at += len(bitmaps[i])
-		}
-	}
-	var app **C.uint64_t
-	if ap != nil {
-		app = &ap[0]
+		defer free()
+		app, aw = &ap[0], w
 	}
 	if e := err(C.wvg_search_group(&hs[0], f32p(qs), C.uint32_t(nq), C.uint32_t(k), app, u64p(aw),
 		u64p(r.IDs), f32p(r.Dists), u32p(r.Counts))); e != nil {
+		return nil, e
+	}
+	return r, nil
+}
+
+// groupAllows: the per-query bitmaps of a grouped call as one C allocation (the
+// pointer table handed to the library may not hold Go pointers): ap[i] nil for a nil
+// list, a non-NULL pointer with zero words for a non-nil empty list.  free releases
+// the block after the call.
+func groupAllows(allows []helpers.AllowList, nq int) (ap []*C.uint64_t, aw []uint64, free func(), e error) {
+	bitmaps := make([][]uint64, nq)
+	total := 1
+	for i, a := range allows {
+		if a == nil || a.IsEmpty() {
+			continue
+		}
+		bitmaps[i] = make([]uint64, a.Max()/64+1)
+		it := a.Iterator()
+		for id, more := it.Next(); more; id, more = it.Next() {
+			bitmaps[i][id/64] |= 1 << (id % 64)
+		}
+		total += len(bitmaps[i])
+	}
+	block := C.calloc(C.size_t(total), 8)
+	if block == nil {
+		return nil, nil, nil, errors.New("out of memory")
+	}
+	words := unsafe.Slice((*uint64)(block), total)
+	ap = make([]*C.uint64_t, nq)
+	aw = make([]uint64, nq)
+	at := 1 // word 0: the target of the empty lists' pointers
+	for i, a := range allows {
+		if a == nil {
+			continue
+		}
+		if bitmaps[i] == nil {
+			ap[i] = (*C.uint64_t)(block)
+			continue
+		}
+		copy(words[at:], bitmaps[i])
+		ap[i] = (*C.uint64_t)(unsafe.Pointer(&words[at]))
+		aw[i] = uint64(len(bitmaps[i]))
+		at += len(bitmaps[i])
+	}
+	return ap, aw, func() { C.free(block) }, nil
+}
+
+// groupHandles: the C handles of a grouped call's corpora (none may be nil).
+func groupHandles(name string, corpora []*Corpus, keep []interface{}) ([]*C.wvg_corpus, []interface{}, error) {
+	hs := make([]*C.wvg_corpus, len(corpora))
+	for i, x := range corpora {
+		if x == nil {
+			return nil, nil, fmt.Errorf("%s[%d] is nil", name, i)
+		}
+		hs[i] = x.h
+		keep = append(keep, x)
+	}
+	return hs, keep, nil
+}
+
+// SearchGroupBQRescore: one flat.searchByVectorBQ (V/flat/index.go:347-389) per
+// query -- query i (qs is len(bq)*dims floats) against tenant i, its BQ codes in
+// bq[i] and its float rows in f32[i] (same dims / idBase / metric), the shards of
+// a multi-tenant BQ class (adapters/repos/db/index.go:1516-1539) -- as three
+// launches whatever the number of queries (wvg_search_group_bq_rescore).  The
+// result is the reference heaps' own, as Corpus.SearchBQRescore's.  allows as
+// SearchGroup: empty, or one list per query, nil meaning no filter and a non-nil
+// empty list an empty result for that query alone.
+func SearchGroupBQRescore(bq, f32 []*Corpus, qs []float32, k, rescoreLimit int, allows []helpers.AllowList) (*Results, error) {
+	nq := len(bq)
+	r := emptyResults(nq, k)
+	if nq == 0 || k == 0 {
+		return r, nil
+	}
+	if bq[0] == nil {
+		return nil, errors.New("nil corpus")
+	}
+	if len(f32) != len(bq) {
+		return nil, errors.New("BQ and F32 corpora don't match")
+	}
+	if len(qs) != len(bq)*bq[0].dims {
+		return nil, errors.New("vector lengths don't match")
+	}
+	if len(allows) != 0 && len(allows) != len(bq) {
+		return nil, errors.New("allow lists don't match the corpora")
+	}
+	hb, keep, e := groupHandles("bq", bq, make([]interface{}, 0, 2*nq))
+	if e != nil {
+		return nil, e
+	}
+	hf, keep, e := groupHandles("f32", f32, keep)
+	if e != nil {
+		return nil, e
+	}
+	defer pin(keep...)()
+	var app **C.uint64_t
+	var aw []uint64
+	if len(allows) != 0 {
+		ap, w, free, e := groupAllows(allows, nq)
+		if e != nil {
+			return nil, e
+		}
+		defer free()
+		app, aw = &ap[0], w
+	}
+	if e := err(C.wvg_search_group_bq_rescore(&hb[0], &hf[0], f32p(qs), C.uint32_t(nq), C.uint32_t(k),
+		C.uint32_t(rescoreLimit), app, u64p(aw), u64p(r.IDs), f32p(r.Dists), u32p(r.Counts))); e != nil {
+		return nil, e
+	}
+	return r, nil
+}
+
+// SearchGroupBQCandidates: the first half of SearchGroupBQRescore for tenants
+// whose float rows stay in the LSM store (V/flat/index.go:355-374): per query the
+// ids and Hamming distances its heap of rescoreLimit holds, in pop order, as
+// Corpus.SearchBQCandidates returns them (wvg_search_group_bq_candidates).
+func SearchGroupBQCandidates(bq []*Corpus, qs []float32, rescoreLimit int, allows []helpers.AllowList) (*Results, error) {
+	nq := len(bq)
+	r := emptyResults(nq, rescoreLimit)
+	if nq == 0 || rescoreLimit == 0 {
+		return r, nil
+	}
+	if bq[0] == nil {
+		return nil, errors.New("nil corpus")
+	}
+	if len(qs) != len(bq)*bq[0].dims {
+		return nil, errors.New("vector lengths don't match")
+	}
+	if len(allows) != 0 && len(allows) != len(bq) {
+		return nil, errors.New("allow lists don't match the corpora")
+	}
+	hb, keep, e := groupHandles("bq", bq, make([]interface{}, 0, nq))
+	if e != nil {
+		return nil, e
+	}
+	defer pin(keep...)()
+	var app **C.uint64_t
+	var aw []uint64
+	if len(allows) != 0 {
+		ap, w, free, e := groupAllows(allows, nq)
+		if e != nil {
+			return nil, e
+		}
+		defer free()
+		app, aw = &ap[0], w
+	}
+	if e := err(C.wvg_search_group_bq_candidates(&hb[0], f32p(qs), C.uint32_t(nq), C.uint32_t(rescoreLimit), app,
+		u64p(aw), u64p(r.IDs), f32p(r.Dists), u32p(r.Counts))); e != nil {
 		return nil, e
 	}
 	return r, nil

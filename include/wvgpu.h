@@ -260,6 +260,31 @@ int wvg_search_bq_rescore(wvg_corpus *bq, wvg_corpus *f32, const float *queries,
 int wvg_search_bq_candidates(wvg_corpus *bq, const float *queries, uint32_t nq, uint32_t rescore_limit,
                              const uint64_t *allow_bits, uint64_t allow_words, uint64_t *out_ids,
                              float *out_dists, uint32_t *out_counts);
+/* nq flat.searchByVectorBQ calls (V/flat/index.go:347-389), query i against
+ * tenant i = (bq[i], f32[i]) -- the shards of a multi-tenant BQ class, one
+ * tenant per query (adapters/repos/db/index.go:1516-1539, 1554-1565) -- in
+ * three launches whatever nq is: a Hamming scan, the filter that finds the rows
+ * findTopVectorsCached's heap can insert (index.go:456-506), the exact rescore
+ * (:375-385).  R = max(rescore_limit, k) (:297-305); any R and any k.  Every
+ * bq[i] is a BQ and every f32[i] an F32 corpus of one context, metric and dim,
+ * bq[i] and f32[i] with one id_base; a tenant may appear any number of times.
+ * allow_bits / allow_words as wvg_search_group (per query, over tenant i's
+ * global docIDs).  Outputs [nq][k] / counts[nq] exactly as nq
+ * wvg_search_bq_rescore(bq[i], f32[i], q_i, 1, k, rescore_limit, allow_i)
+ * calls would write them -- the reference heaps' result, ties included.
+ * heap_replay = 0, or dim above 8192: WVG_ERR_UNSUPPORTED.                 */
+int wvg_search_group_bq_rescore(wvg_corpus *const *bq, wvg_corpus *const *f32, const float *queries,
+                                uint32_t nq, uint32_t k, uint32_t rescore_limit,
+                                const uint64_t *const *allow_bits, const uint64_t *allow_words,
+                                uint64_t *out_ids, float *out_dists, uint32_t *out_counts);
+/* The first half only, for callers whose float rows are not on the GPU
+ * (V/flat/index.go:355-374): per query what wvg_search_bq_candidates(bq[i],
+ * q_i, 1, rescore_limit, allow_i) writes -- [nq][rescore_limit] ids / Hamming
+ * distances in the heap's pop order, counts[nq].                           */
+int wvg_search_group_bq_candidates(wvg_corpus *const *bq, const float *queries, uint32_t nq,
+                                   uint32_t rescore_limit, const uint64_t *const *allow_bits,
+                                   const uint64_t *allow_words, uint64_t *out_ids, float *out_dists,
+                                   uint32_t *out_counts);
 
 /* flat.SearchByVectorDistance (V/flat/index.go:531-591): every row with
  * dist <= target_distance or |dist - target| <= 1e-6 (floatcomp.InDelta,

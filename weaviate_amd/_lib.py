@@ -83,6 +83,10 @@ SIGNATURES = {
                                       _P(c_uint64), c_uint64, _P(c_uint64), _P(c_float), _P(c_uint32)]),
     "wvg_search_bq_candidates": (c_int, [c_void_p, _P(c_float), c_uint32, c_uint32, _P(c_uint64), c_uint64,
                                          _P(c_uint64), _P(c_float), _P(c_uint32)]),
+    "wvg_search_group_bq_rescore": (c_int, [_P(c_void_p), _P(c_void_p), _P(c_float), c_uint32, c_uint32, c_uint32,
+                                            _P(c_void_p), _P(c_uint64), _P(c_uint64), _P(c_float), _P(c_uint32)]),
+    "wvg_search_group_bq_candidates": (c_int, [_P(c_void_p), _P(c_float), c_uint32, c_uint32, _P(c_void_p),
+                                               _P(c_uint64), _P(c_uint64), _P(c_float), _P(c_uint32)]),
     "wvg_search_by_distance": (c_int, [c_void_p, _P(c_float), c_float, ctypes.c_int64, _P(c_uint64), c_uint64,
                                        _P(c_uint64), _P(c_float), c_uint64, _P(c_uint64)]),
     "wvg_search_by_distance_window": (c_int, [c_void_p, _P(c_float), c_float, c_uint32, _P(c_uint64), c_uint64,

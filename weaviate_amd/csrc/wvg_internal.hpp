@@ -371,7 +371,8 @@ struct GroupQuery {
     uint64_t allow_off;      // the query's window: word offset into the call's allow block,
     uint64_t allow_words;    // its length in words (tiles) and the tile of its word 0
     uint64_t allow_t0;
-    uint32_t list0, nlists;  // the query's lists in `partials` (nlists = 0: nothing live or allowed)
+    uint32_t list0, nlists;  // the query's lists in `partials` (nlists = 0: nothing live or allowed); the grouped
+                             // BQ flow (wvg_group_bq.hip): its first tile in the call's strips, and its items
     uint32_t filtered, pad;  // 1: the allow window applies
 };
 static_assert(sizeof(GroupQuery) == 80, "descriptor layout shared by host and device");

@@ -254,6 +254,29 @@ class Corpus:
         return ids[:cnt.value], dists[:cnt.value]
 
 
+def _group_allows(allows, nq):
+    """The per-query allow tables of the grouped calls: (pointer table, word counts,
+    the arrays to keep alive), or (None, None, []) for allows = None.  An empty array
+    is a non-NULL pointer with 0 words: nothing allowed for that query."""
+    if allows is None:
+        return None, None, []
+    ap = (c_void_p * max(nq, 1))()
+    aw = np.zeros(max(nq, 1), dtype=np.uint64)
+    keep = []
+    for i, a in enumerate(allows):
+        if a is None:
+            continue
+        words = np.ascontiguousarray(a, dtype=np.uint64)
+        if words.size == 0:  # non-NULL with 0 words: nothing allowed
+            words = np.zeros(1, dtype=np.uint64)
+            aw[i] = 0
+        else:
+            aw[i] = words.size
+        keep.append(words)
+        ap[i] = words.ctypes.data
+    return ap, aw, keep
+
+
 def search_group(corpora, queries, k: int, allows=None):
     """wvg_search_group: query i against corpora[i] (the tenants of one class: F32,
     one context, one metric, one dim), all in one scan launch and one merge launch.
@@ -274,24 +297,55 @@ def search_group(corpora, queries, k: int, allows=None):
     ids = np.empty((nq, k), dtype=np.uint64)
     dists = np.empty((nq, k), dtype=np.float32)
     counts = np.empty(nq, dtype=np.uint32)
-    ap = aw = None
-    keep = []  # the bitmaps, alive through the call
-    if allows is not None:
-        ap = (c_void_p * max(nq, 1))()
-        aw = np.zeros(max(nq, 1), dtype=np.uint64)
-        for i, a in enumerate(allows):
-            if a is None:
-                continue
-            words = np.ascontiguousarray(a, dtype=np.uint64)
-            if words.size == 0:  # non-NULL with 0 words: nothing allowed
-                words = np.zeros(1, dtype=np.uint64)
-                aw[i] = 0
-            else:
-                aw[i] = words.size
-            keep.append(words)
-            ap[i] = words.ctypes.data
+    ap, aw, keep = _group_allows(allows, nq)  # keep: the bitmaps, alive through the call
     check(lib.wvg_search_group(handles, fptr(q), nq, k, ap, u64ptr(aw) if aw is not None else None,
                                u64ptr(ids), fptr(dists), u32ptr(counts)))
+    return ids, dists, counts
+
+
+def _group_bq_args(bqs, queries, allows):
+    bqs = list(bqs)
+    nq = len(bqs)
+    q = np.ascontiguousarray(queries, dtype=np.float32)
+    if q.ndim == 1:
+        q = q[None, :]
+    if q.shape[0] != nq:
+        raise ValueError(f"{q.shape[0]} queries for {nq} corpora")
+    if allows is not None and len(allows) != nq:
+        raise ValueError(f"{len(allows)} allow lists for {nq} corpora")
+    handles = (c_void_p * max(nq, 1))(*[c.handle if c is not None else None for c in bqs])
+    return nq, q, handles, _group_allows(allows, nq)
+
+
+def search_group_bq_rescore(bqs, f32s, queries, k: int, rescore_limit: int, allows=None):
+    """wvg_search_group_bq_rescore: flat.searchByVectorBQ of query i against tenant
+    (bqs[i], f32s[i]) -- BQ and F32 corpora of one context, metric and dim -- all in
+    three launches.  allows as search_group.  Returns (ids [nq][k], dists [nq][k],
+    counts [nq]), as nq search_bq_rescore calls would."""
+    f32s = list(f32s)
+    nq, q, hb, (ap, aw, keep) = _group_bq_args(bqs, queries, allows)
+    if len(f32s) != nq:
+        raise ValueError(f"{len(f32s)} F32 corpora for {nq} BQ corpora")
+    hf = (c_void_p * max(nq, 1))(*[c.handle if c is not None else None for c in f32s])
+    ids = np.empty((nq, k), dtype=np.uint64)
+    dists = np.empty((nq, k), dtype=np.float32)
+    counts = np.empty(nq, dtype=np.uint32)
+    check(_lib.load().wvg_search_group_bq_rescore(hb, hf, fptr(q), nq, k, rescore_limit, ap,
+                                                  u64ptr(aw) if aw is not None else None,
+                                                  u64ptr(ids), fptr(dists), u32ptr(counts)))
+    return ids, dists, counts
+
+
+def search_group_bq_candidates(bqs, queries, rescore_limit: int, allows=None):
+    """wvg_search_group_bq_candidates: per query the heap's candidates in pop order,
+    as nq search_bq_candidates calls: (ids [nq][R], dists [nq][R], counts [nq])."""
+    nq, q, hb, (ap, aw, keep) = _group_bq_args(bqs, queries, allows)
+    R = rescore_limit
+    ids = np.empty((nq, R), dtype=np.uint64)
+    dists = np.empty((nq, R), dtype=np.float32)
+    counts = np.empty(nq, dtype=np.uint32)
+    check(_lib.load().wvg_search_group_bq_candidates(hb, fptr(q), nq, R, ap, u64ptr(aw) if aw is not None else None,
+                                                     u64ptr(ids), fptr(dists), u32ptr(counts)))
     return ids, dists, counts
 
 

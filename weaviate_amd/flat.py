@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import KIND_BQ, KIND_F32, METRIC_BY_NAME, WVG_ERR_DIM_MISMATCH, WvgError
-from .device import Corpus, allow_bitmap, search_bq_rescore, search_group
+from .device import Corpus, allow_bitmap, search_bq_rescore, search_group, search_group_bq_rescore
 from .distancer import provider_for
 
 DEFAULT_SEARCH_BY_DIST_INITIAL_LIMIT = 100  # V/common/search_by_dist_params.go:17
@@ -285,16 +285,20 @@ class FlatIndex:
 def SearchByVectorGroup(indexes, vectors, k: int, allows=None):
     """One SearchByVector per (index, vector) pair -- the tenants of a multi-tenant
     class, whose queries each name one shard (adapters/repos/db/index.go:1516-1539) --
-    as one grouped device call (wvg_search_group).  indexes: uncompressed FlatIndex
-    objects of one context, distance and dims; allows: None or one AllowList / None
-    per query (an empty list: no results for that query, as SearchByVector).  Returns
-    [(ids, dists)] per query, trimmed to its result count."""
+    as one grouped device call.  indexes: FlatIndex objects of one context, distance
+    and dims, either all uncompressed (wvg_search_group) or all BQ-compressed with one
+    searchTimeRescore(k) (wvg_search_group_bq_rescore: searchByVectorBQ per tenant);
+    allows: None or one AllowList / None per query (an empty list: no results for that
+    query, as SearchByVector).  Returns [(ids, dists)] per query, trimmed to its result
+    count."""
     indexes = list(indexes)
     if k < 0:
         raise ValueError("k must be >= 0")
-    for ix in indexes:
-        if ix.bq is not None:
-            raise ValueError("SearchByVectorGroup: compressed flat indexes are searched one by one")
+    compressed = [ix.bq is not None for ix in indexes]
+    if any(compressed) and not all(compressed):
+        raise ValueError("SearchByVectorGroup: compressed and uncompressed flat indexes in one call")
+    if any(compressed) and len({ix.searchTimeRescore(k) for ix in indexes}) != 1:
+        raise ValueError("SearchByVectorGroup: compressed flat indexes with different rescore limits")
     if allows is not None and len(allows) != len(indexes):
         raise ValueError("indexes and allows sizes does not match")
     bms = None
@@ -302,8 +306,38 @@ def SearchByVectorGroup(indexes, vectors, k: int, allows=None):
         bms = [None if a is None else (np.empty(0, dtype=np.uint64) if a.IsEmpty() else a.bitmap()) for a in allows]
     if not indexes:
         return []
-    ids, dists, counts = search_group([ix.vectors for ix in indexes], vectors, k, bms)
+    if any(compressed):
+        ids, dists, counts = search_group_bq_rescore([ix.bq for ix in indexes], [ix.vectors for ix in indexes],
+                                                     vectors, k, indexes[0].searchTimeRescore(k), bms)
+    else:
+        ids, dists, counts = search_group([ix.vectors for ix in indexes], vectors, k, bms)
     return [(ids[i, :int(counts[i])], dists[i, :int(counts[i])]) for i in range(len(indexes))]
+
+
+def group_bq_kept_rows(dists, valid, R: int, chunk: int = 256):
+    """The filter rule of the grouped BQ flow (bq_group_filter_kernel, DESIGN.md §5
+    "Grouped BQ search over tenants"), restated: which rows of one query's distance
+    strip go to the host heap.
+
+    The heap of R over docIDs in ascending order inserts row i iff fewer than R live
+    allowed rows precede it or d_i < T_i, T_i the R-th smallest distance of all
+    earlier live allowed rows.  The filter walks the rows in chunks of `chunk`; T at a
+    chunk's start is the R-th smallest distance of the live allowed rows before the
+    chunk (+inf while there are fewer than R), and a live row of the chunk is kept iff
+    d_i < T.  T_i is the R-th smallest over a prefix that contains the chunk's, so
+    T_i <= T: the kept rows are a superset of the inserted ones, and replaying them in
+    docID order reproduces the heap.  With chunk = 1, T = T_i and the kept rows are
+    exactly the inserted ones.  Returns a bool mask.
+    """
+    d = np.asarray(dists, dtype=np.float32)
+    live = np.ones(len(d), bool) if valid is None else np.asarray(valid).astype(bool)
+    keep = np.zeros(len(d), bool)
+    for c0 in range(0, len(d), chunk):
+        c1 = min(c0 + chunk, len(d))
+        before = d[:c0][live[:c0]]
+        thr = np.partition(before, R - 1)[R - 1] if len(before) >= R else np.float32(np.inf)
+        keep[c0:c1] = live[c0:c1] & (d[c0:c1] < thr)
+    return keep
 
 
 def multi_bq_kept_rows(dists, valid, R: int, slab: int, range_rows: int):

@@ -336,7 +336,11 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
  * 16 queries (k <= 64; 8 for k <= 128, 4 above; d = 768: 4, 2 above 128) and
  * every query of the pass is scored against each row while it is in
  * registers; one merge workgroup per query merges its partial lists in the
- * same launch.  Everywhere else (one query, other metrics or dims,
+ * same launch.  A short prologue launch on the same stream prepares that
+ * scan's part of the workspace (its hand-off words and, where every wave
+ * scans only a few tiles, per query the k-th distance of a sample of the
+ * first rows, which bounds the scan's lists from the start; the results do
+ * not depend on it).  Everywhere else (one query, other metrics or dims,
  * cache_reuse = 0) every query is one full scan of the corpus: the scan
  * workgroups walk the queries back to back and one extra workgroup merges
  * each query's lists while the scan moves on.  F32 corpora; same workspace

@@ -457,7 +457,8 @@ int wvgx_filtered_timing(uint64_t *out5, int reset)
 // 20 = screen kernel (0 K3d where it applies, 1 K3c), 21 = screen pilot seed, 22 = exact seeds between
 // screen phases, 23 = K3b pilot tiles, 24 = single-query host path, ..., 29 / 30 = K3i warm-up range
 // blocks (first / second phase), 31 = filtered batches' windows from pinned staging, 32 = K3i's K3b pilot tiles,
-// 33 = screen ranges in whole rounds of the CUs, ..., 36 = the multi-GPU BQ flow's cross-slab bound.
+// 33 = screen ranges in whole rounds of the CUs, ..., 36 = the multi-GPU BQ flow's cross-slab bound,
+// 37 / 38 = the shared-row scan's sample tiles and the tiles-per-wave limit of seeding, 39 = its batched combine.
 // Returns the previous value.
 int wvgx_set_tuning(int key, int value)
 {
@@ -574,6 +575,15 @@ int wvgx_set_tuning(int key, int value)
     } else if (key == 36) {
         old = t.multi_bq_bound;
         t.multi_bq_bound = value;
+    } else if (key == 37 && value >= 0) {
+        old = t.qshare_seed;
+        t.qshare_seed = value;
+    } else if (key == 38 && value >= 0) {
+        old = t.qshare_seed_tpw;
+        t.qshare_seed_tpw = value;
+    } else if (key == 39) {
+        old = t.qshare_combine;
+        t.qshare_combine = value;
     }
     return old;
 }

@@ -333,9 +333,19 @@ hipError_t launch_scan_f32_stream(const ScanArgs &a, const StreamJob &j, hipStre
 // qshare_queries_per_pass() at a time; a pass walks the wave's tiles once
 // (direction (reverse + pass) & 1) and scores every query of the pass against each
 // tile, then publishes one list per query: partials [nq][groups][k] with ready
-// words [nq][groups] (zeroed per call; 1 = published).  Merger m merges queries
-// m, m + mergers, ... with the bounded poll of merge_lists_ready; on expiry that
-// query gets empty results and WVG_STATUS_MERGE_TIMEOUT is set in *status.
+// words [nq][groups] (1 = published).  At the end of a pass every wave leaves its
+// lists in LDS and wave w merges and publishes the pass's queries w, w + 4, ...
+// Merger m merges queries m, m + mergers, ... with the bounded poll of
+// merge_lists_ready; on expiry that query gets empty results and
+// WVG_STATUS_MERGE_TIMEOUT is set in *status.
+// A prologue launch (qshare_seed_kernel, stream order before the scan) zeroes
+// the ready words and writes seeds[q]: the k-th smallest key of query q over the
+// first seed_tiles tiles of [tile_begin, tile_end), scored with the scan's own
+// chain (KEY_NONE with fewer than k live rows there, or with seed_tiles = 0).
+// The sample is part of the scanned rows, so its k-th key is an upper bound of
+// the result's k-th key: the scan's lists start with tau = seed + 1 and a wave
+// sorts or inserts only the rows at or below the seed key, not the first k it
+// meets.  The host seeds where a wave has few tiles (qshare_seed_tiles).
 struct QShareArgs {
     const void *data;        // tiled corpus
     const uint64_t *valid;   // one word per tile
@@ -352,10 +362,16 @@ struct QShareArgs {
     uint32_t reverse;        // direction of pass 0
     uint32_t plain, cache_tail256;  // as ScanArgs
     int metric;
+    uint64_t *seeds;         // [nq] sample k-th keys, written by the prologue
+    uint32_t seed_tiles;     // tiles of the sample (0 = none: open bounds)
+    uint32_t seq_combine;    // tools A/B: one group_combine_publish per query instead of the pass's batched combine
 };
 bool qshare_supported(int metric, uint32_t dim, int order512);
 uint32_t qshare_queries_per_pass(uint32_t dim, uint32_t k);
 uint32_t qshare_groups(uint64_t ntiles, int num_cus);
+// Tiles of the prologue's sample for a scan of ntiles tiles by `groups` workgroups (0 = no seeding).
+uint32_t qshare_seed_tiles(uint32_t dim, uint64_t ntiles, uint32_t groups);
+hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s);
 hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s);
 // Grouped search (wvg_search_group, wvg_group.hip): nq single-query scans, query i
 // over a corpus of its own, as ONE scan launch and one merge launch.  The host
@@ -579,6 +595,15 @@ struct Tuning {
                              // (4 queries per pass) at d = 128 too (A/B)
     int qshare_mergers = 0;  // its merge workgroups (tuning key 35): 0 = one per query (at most 64), n = n (1 = the
                              // queries merged one after another; A/B)
+    int qshare_seed = 32;    // shared-row scan (tuning key 37): tiles of the prologue's row sample whose k-th key
+                             // bounds every wave's list from the start; 0 = no seeding (A/B).  1M x 128, 16 queries:
+                             // 16 / 32 / 64 / 128 tiles -> 83.7k / 84.2k / 82.2k / 75.4k QPS, 64.8k without
+                             // (profiles/r11/qshare_seed/: the prologue costs ~0.3 us per tile)
+    int qshare_seed_tpw = 124;  // (tuning key 38) seed only while a wave scans at most this many tiles,
+                                // ntiles / (groups x SCAN_WAVES): the saving is a fixed ~80-110 us per launch
+                                // (+29 % at 8, +10 % at 30, +4 % at 122 tiles per wave, the largest measured)
+    int qshare_combine = 1;  // (tuning key 39) 1 = the pass's lists combined in one step, every wave merging its
+                             // share of the queries; 0 = one group_combine_publish per query on wave 0 (A/B)
     int multi_bq_bound = 1;  // multi-GPU BQ heap flow (tuning key 36): 1 = the cross-slab bound X_s in the filter,
                              // 0 = every slab filters with its own thresholds only (A/B: rows replayed)
     int screen_diag = 0;     // K3c diagnostics (tools build only; results are NOT distances): bit 0 = no

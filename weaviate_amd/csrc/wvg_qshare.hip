@@ -20,6 +20,13 @@
 // ids, so every workgroup they wait for is dispatched before them.
 // Roofline: one HBM read of the rows per pass against nq x rows x d (sub, fma)
 // pairs on the VALU.
+// A wave of the 1M-row scan owns only ~8 tiles, so a list that starts empty
+// never reaches the steady state where a batch is rejected by one compare: per
+// query it pays a 64-key sort + merge on its first tile and a couple of dozen
+// single inserts after it, and nearly all of those keys are dropped by the
+// mergers.  qshare_seed_kernel (launched before the scan, in place of the
+// memset of the ready words) scores a sample of the first tiles and leaves the
+// sample's k-th key per query; the lists start from that bound (QShareArgs).
 #include <algorithm>
 
 #include "wvg_internal.hpp"
@@ -80,6 +87,107 @@ constexpr int qshare_qp(int d, int e, bool whole)
     return whole ? (e == 1 ? 16 : (e == 2 ? 8 : 4)) : (d > 128 && e == 4 ? 2 : 4);
 }
 
+// The bound of a query's lists from its seed: seed + 1, so that `key < bound`
+// admits the seed row itself (the wave that owns it scans it again); an open
+// seed (KEY_NONE) stays open.
+__device__ __forceinline__ uint64_t seed_bound(cu64 *seed)
+{
+    const uint64_t s = *seed;
+    return s + (s != WVG_KEY_NONE ? 1ull : 0ull);
+}
+
+// The prologue of a shared-row launch.  The grid zeroes the ready words; then
+// workgroup q scores the first a.seed_tiles tiles of the range for query q -- a
+// wave the tiles wave, wave + SEED_WAVES, ..., with the scan's validity words
+// and the scan's chain (chunk_update2 in chunk order, avx256_reduce2,
+// wrap_metric, lane_key: the keys are the scan's bit for bit) -- and writes the
+// sample's k-th smallest key to seeds[q], KEY_NONE with fewer than k live rows.
+constexpr int SEED_WAVES = 16;
+template <int METRIC, int D, int E>
+__global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs a)
+{
+    static_assert(D % 32 == 0 && D > 0 && !is_abs_or_neq<METRIC>, "shared rows: fixed D, the AVX2 chains");
+    constexpr int NC = D / 4;
+    const uint64_t nready = (uint64_t)a.nq * a.groups;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nready; i += (uint64_t)gridDim.x * blockDim.x)
+        a.ready[i] = 0u;
+    const uint32_t q = blockIdx.x;  // gridDim.x == nq
+    const uint64_t ntiles = a.tile_end - a.tile_begin;
+    const uint64_t ns = a.seed_tiles < ntiles ? a.seed_tiles : ntiles;
+    if (ns == 0) {  // workgroup-uniform
+        if (threadIdx.x == 0) a.seeds[q] = WVG_KEY_NONE;
+        return;
+    }
+    const int lane = threadIdx.x & 63, wave = wave_id();
+    const float4 *data = reinterpret_cast<const float4 *>(a.data);
+    cu64 *valid = (cu64 *)a.valid;
+    cf4 *qj = (cf4 *)a.queries + (size_t)q * (a.qpitch / 4);
+    WaveTopK<E> tk;
+    tk.init((int)a.k);
+    for (uint64_t t = a.tile_begin + (uint64_t)wave; t < a.tile_begin + ns; t += SEED_WAVES) {
+        const uint64_t m = valid[t];
+        if (m == 0ull) continue;  // wave-uniform
+        const float4 *rp = data + (size_t)t * NC * 64 + lane;
+        f2v acc[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int p = 0; p < 4; p++) acc[r][p] = f2v{0.0f, 0.0f};
+#pragma unroll 2
+        for (int b = 0; b < D / 32; b++) {
+            float4 xs[8];
+#pragma unroll
+            for (int cc = 0; cc < 8; cc++) xs[cc] = rp[(size_t)(b * 8 + cc) * 64];  // default policy: the scan reads them again
+#pragma unroll
+            for (int cc = 0; cc < 8; cc++) chunk_update2<METRIC>(acc, cc, qj[b * 8 + cc], xs[cc]);
+        }
+        tk.offer(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane));
+    }
+    const uint64_t kth = group_combine_kth<E, SEED_WAVES>(tk);
+    if (threadIdx.x == 0) a.seeds[q] = kth;
+}
+
+// The end of a pass: every wave leaves its QP lists in LDS, then wave w merges
+// the SCAN_WAVES lists of the pass's queries w, w + SCAN_WAVES, ... and publishes
+// each as group_combine_publish does (write-through stores, the storing wave's
+// own drain, then the list's ready word).  Keys are unique, so the merge order
+// does not change a list.
+template <int E, int QP>
+__device__ __forceinline__ void pass_combine_publish(WaveTopK<E> (&tk)[QP], uint32_t nqp, uint32_t k, uint64_t *partials,
+                                                     uint32_t *ready, size_t list0, uint32_t G, bool more)
+{
+    __shared__ uint64_t psh[QP][SCAN_WAVES][64 * E];
+    const int lane = threadIdx.x & 63;
+    const int wave = wave_id();
+#pragma unroll
+    for (int j = 0; j < QP; j++)
+#pragma unroll
+        for (int e = 0; e < E; e++) psh[j][wave][e * 64 + lane] = tk[j].l[e];
+    __syncthreads();
+    for (uint32_t j = (uint32_t)wave; j < nqp; j += SCAN_WAVES) {
+        uint64_t l[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) l[e] = psh[j][0][e * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < SCAN_WAVES; w++) {
+            uint64_t o[E];
+#pragma unroll
+            for (int e = 0; e < E; e++) o[e] = psh[j][w][e * 64 + lane];
+            merge_lists<E>(l, o);
+        }
+        const size_t li = list0 + (size_t)j * G;
+        uint64_t *out = partials + li * k;
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const uint32_t i = e * 64 + lane;
+            if (i < k) __hip_atomic_store((gu64 *)(out + i), l[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_store((gu32 *)(ready + li), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (more) __syncthreads();  // psh is reused by the next pass
+}
+
 // (two waves per SIMD -- at most 256 registers -- so one wave's tile loads run under the other's folds)
 template <int METRIC, int D, int E, bool WHOLE>
 __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_kernel(
@@ -117,9 +225,11 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
     for (uint32_t q0 = 0, pass = 0; q0 < a.nq; q0 += QP, pass++) {
         const uint32_t nqp = a.nq - q0 < (uint32_t)QP ? a.nq - q0 : (uint32_t)QP;  // queries of this pass
         const bool rev = ((a.reverse + pass) & 1u) != 0;  // serpentine over the passes
+        // seeds: written by the prologue launch, read-only here (wave-uniform scalar loads)
+        cu64 *sd = (cu64 *)a.seeds + q0;
         WaveTopK<E> tk[QP];
 #pragma unroll
-        for (int j = 0; j < QP; j++) tk[j].init((int)a.k);
+        for (int j = 0; j < QP; j++) tk[j].init_bounded((int)a.k, (uint32_t)j < nqp ? seed_bound(sd + j) : WVG_KEY_NONE);
         cf4 *qb = (cf4 *)a.queries + (size_t)q0 * qstride;
         uint64_t m_next = n ? valid[rev ? t1 - 1 : t0] : 0ull;
         for (uint64_t i = 0; i < n; ++i) {
@@ -162,7 +272,8 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
                             for (int c = 0; c < 4; c++) qc[c] = qn[c];
                         }
-                        tk[j].offer(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane));
+                        tk[j].offer_bounded(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane),
+                                            [&] { return seed_bound(sd + j); });
                     }
                 }
             } else {
@@ -197,16 +308,23 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
                 for (int j = 0; j < QP; j++)
                     if ((uint32_t)j < nqp)
-                        tk[j].offer(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc[j])), t, lane));
+                        tk[j].offer_bounded(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc[j])), t, lane),
+                                            [&] { return seed_bound(sd + j); });
             }
         }
+#ifdef WVG_TOOLS
+        if (a.seq_combine) {  // A/B: the queries combined one after another, wave 0 merging
 #pragma unroll
-        for (int j = 0; j < QP; j++) {
-            if ((uint32_t)j < nqp) {  // workgroup-uniform
-                const size_t li = (size_t)(q0 + j) * G + blockIdx.x;
-                group_combine_publish<E, SCAN_WAVES>(tk[j], a.partials + li * a.k, nullptr, a.ready + li, 1u);
+            for (int j = 0; j < QP; j++) {
+                if ((uint32_t)j < nqp) {  // workgroup-uniform
+                    const size_t li = (size_t)(q0 + j) * G + blockIdx.x;
+                    group_combine_publish<E, SCAN_WAVES>(tk[j], a.partials + li * a.k, nullptr, a.ready + li, 1u);
+                }
             }
+            continue;
         }
+#endif
+        pass_combine_publish<E, QP>(tk, nqp, a.k, a.partials, a.ready, (size_t)q0 * G + blockIdx.x, G, q0 + QP < a.nq);
     }
 }
 
@@ -236,6 +354,44 @@ uint32_t qshare_groups(uint64_t ntiles, int num_cus)
 {
     const uint64_t g = std::min<uint64_t>((uint64_t)num_cus * 2, (ntiles + SCAN_WAVES - 1) / SCAN_WAVES);
     return (uint32_t)std::max<uint64_t>(g, 1);
+}
+
+// Seeding pays where a wave's range is short (at most qshare_seed_tpw tiles per
+// wave; with long ranges the lists' start-up is nothing beside the scan) and the
+// scan is bound by the VALU: at d = 768 a pass is bound by HBM, the start-up
+// hides under the loads and the sample costs 6x the reads (1M x 768, 16
+// queries: launch 1789 -> 1799 us, prologue 145 us), so only d = 128 is seeded.
+uint32_t qshare_seed_tiles(uint32_t dim, uint64_t ntiles, uint32_t groups)
+{
+    const Tuning &t = tuning();
+    if (t.qshare_seed <= 0 || dim != 128 || groups == 0) return 0;
+    if (ntiles / ((uint64_t)groups * SCAN_WAVES) > (uint64_t)t.qshare_seed_tpw) return 0;
+    return (uint32_t)std::min<uint64_t>((uint64_t)t.qshare_seed, ntiles);
+}
+
+template <int METRIC, int E>
+static hipError_t launch_seed_e(const QShareArgs &a, hipStream_t s)
+{
+    dim3 grid(a.nq), block(SEED_WAVES * 64);
+    if (a.dim == 128)
+        hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 128, E>), grid, block, 0, s, a);
+    else if (a.dim == 768)
+        hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 768, E>), grid, block, 0, s, a);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s)
+{
+    if (!qshare_supported(a.metric, a.dim, 0) || a.nq == 0) return hipErrorInvalidValue;
+    auto go = [&](auto M) -> hipError_t {
+        constexpr int MM = decltype(M)::value;
+        if (a.k <= 64) return launch_seed_e<MM, 1>(a, s);
+        if (a.k <= 128) return launch_seed_e<MM, 2>(a, s);
+        return launch_seed_e<MM, 4>(a, s);
+    };
+    return a.metric == WVG_M_L2 ? go(MetricTag<WVG_M_L2>{}) : go(MetricTag<WVG_M_DOT>{});
 }
 
 template <int METRIC, int E>

@@ -1286,9 +1286,10 @@ static StreamLayout stream_layout(const SearchPlan &p1, uint32_t nq, uint32_t k)
 }
 
 // Workspace of the shared-row query stream (after the status block): partial
-// lists [nq][groups][k], then the ready words [nq][groups] (zeroed per call).
+// lists [nq][groups][k], the ready words [nq][groups] (zeroed per call by the
+// prologue launch), then the prologue's seeds [nq] (8 bytes each).
 struct QShareLayout {
-    size_t partials = 0, ready = 0, total = 0;
+    size_t partials = 0, ready = 0, seeds = 0, total = 0;
     uint32_t groups = 0;
 };
 static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k)
@@ -1297,7 +1298,8 @@ static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uin
     l.groups = qshare_groups(p1.te - p1.tb, c->ctx->num_cus);
     l.partials = WS_STATUS_BYTES;
     l.ready = l.partials + align_up((size_t)nq * l.groups * k * 8, 256);
-    l.total = l.ready + align_up((size_t)nq * l.groups * 4, 256);
+    l.seeds = l.ready + align_up((size_t)nq * l.groups * 4, 256);
+    l.total = l.seeds + align_up((size_t)nq * 8, 256);
     return l;
 }
 
@@ -1388,7 +1390,10 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
         a.cache_tail256 = k1_cache_tail(c, p.tb, p.te);
         a.metric = c->metric;
         const uint32_t mergers = tuning().qshare_mergers > 0 ? (uint32_t)tuning().qshare_mergers : std::min<uint32_t>(nq, 64);
-        WVG_HIP(hipMemsetAsync(a.ready, 0, l.total - l.ready, s));
+        a.seeds = (uint64_t *)(w + l.seeds);
+        a.seed_tiles = qshare_seed_tiles(c->dim, p.te - p.tb, l.groups);
+        a.seq_combine = tuning().qshare_combine == 0;
+        WVG_HIP(launch_qshare_seed(a, s));  // zeroes the ready words, writes the seeds
         ProfArm arm(c->ctx);
         if (arm.rc) return arm.rc;
         WVG_HIP(launch_scan_f32_qshare(a, mergers, s));

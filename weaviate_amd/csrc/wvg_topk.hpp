@@ -293,6 +293,42 @@ struct WaveTopK {
             }
         }
     }
+
+    // offer() under an outer bound (the shared-row scan's sample seed, wvg_qshare.hip):
+    // the list starts with tau = bound instead of KEY_NONE and tau stays
+    // min(element K-1, bound), so a key at or above the bound never enters and the
+    // list may end shorter than K.  bound_of() yields the wave-uniform bound; it is
+    // called on the accepting path only (the caller re-reads it there instead of
+    // holding it in registers through the scan).
+    __device__ __forceinline__ void init_bounded(int k_, uint64_t bound)
+    {
+        init(k_);
+        tau = bound;
+    }
+    template <typename B>
+    __device__ __forceinline__ void offer_bounded(uint64_t key, B bound_of)
+    {
+        uint64_t mask = __ballot(key < tau);  // wave-uniform
+        if (mask == 0ull) return;
+        const uint64_t bound = bound_of();
+        if (__popcll(mask) > TOPK_INSERT_MAX) {
+            sort64(key);
+            merge_sorted64<E>(l, key);
+            refresh_tau();
+            tau = tau < bound ? tau : bound;
+            return;
+        }
+        while (mask) {
+            const int c = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const uint64_t x = readlane64(key, c);
+            if (x < tau) {
+                insert_one<E>(l, x);
+                refresh_tau();
+                tau = tau < bound ? tau : bound;
+            }
+        }
+    }
 };
 
 // Workgroup combine: WAVES wave lists -> one sorted list in wave 0, which
@@ -334,6 +370,36 @@ __device__ __forceinline__ void group_combine_store(WaveTopK<E> &tk, uint64_t *o
         const int i = e * 64 + lane;
         if (i < tk.k) out[i] = tk.l[e];
     }
+}
+
+// group_combine_store's tree, then the workgroup's K-th smallest key (KEY_NONE
+// with fewer than K keys) instead of the list: valid in wave 0 only.
+template <int E, int WAVES>
+__device__ __forceinline__ uint64_t group_combine_kth(WaveTopK<E> &tk)
+{
+    static_assert((WAVES & (WAVES - 1)) == 0 && WAVES > 1, "WAVES must be a power of two");
+    __shared__ uint64_t sh[WAVES][64 * E];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#pragma unroll
+    for (int e = 0; e < E; e++) sh[wave][e * 64 + lane] = tk.l[e];
+    __syncthreads();
+#pragma unroll
+    for (int half = WAVES / 2; half >= 1; half /= 2) {
+        if (wave < half) {
+            uint64_t o[E];
+#pragma unroll
+            for (int e = 0; e < E; e++) o[e] = sh[wave + half][e * 64 + lane];
+            merge_lists<E>(tk.l, o);
+            if (half > 1) {
+#pragma unroll
+                for (int e = 0; e < E; e++) sh[wave][e * 64 + lane] = tk.l[e];
+            }
+        }
+        if (half > 1) __syncthreads();
+    }
+    tk.refresh_tau();
+    return tk.tau;
 }
 
 }  // namespace wvg

@@ -65,7 +65,10 @@ typedef struct wvg_corpus wvg_corpus;
 int wvg_abi_version(void);
 const char *wvg_last_error(void);
 int wvg_device_count(int *out);
-/* One context per GPU (one process per GPU in the multi-GPU deployment). */
+/* One context per GPU (one process per GPU in the multi-GPU deployment).
+ * Environment, read when a context opens: WVG_QSHARE_SCREEN=0 switches off the
+ * bf16 screen of wvg_search_device_pipelined's shared-row scan for that context
+ * (results are identical either way; the screen only saves time). */
 int wvg_open(int device, wvg_ctx **out);
 /* Context options, fixed for the life of the context (wvg_open uses the
  * defaults).  Fill with wvg_options_default, change fields, then open.     */

@@ -248,6 +248,8 @@ int wvg_open_ex(int device, const wvg_options *opts, wvg_ctx **out)
     c->device = device;
     c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     c->opt = o;
+    // the shared-row scan's screen can be switched off per context (results are the same either way)
+    if (const char *e = getenv("WVG_QSHARE_SCREEN")) c->qshare_screen = (int)strtol(e, nullptr, 10) != 0;
 #ifdef WVG_TOOLS
     if (const char *e = getenv("WVG_MFMA_MIN_QUERIES")) c->opt.mfma_min_queries = (uint32_t)strtoul(e, nullptr, 10);
     if (const char *e = getenv("WVG_SERPENTINE")) tuning().serpentine = (int)strtol(e, nullptr, 10);  // A/B runs
@@ -458,7 +460,8 @@ int wvgx_filtered_timing(uint64_t *out5, int reset)
 // screen phases, 23 = K3b pilot tiles, 24 = single-query host path, ..., 29 / 30 = K3i warm-up range
 // blocks (first / second phase), 31 = filtered batches' windows from pinned staging, 32 = K3i's K3b pilot tiles,
 // 33 = screen ranges in whole rounds of the CUs, ..., 36 = the multi-GPU BQ flow's cross-slab bound,
-// 37 / 38 = the shared-row scan's sample tiles and the tiles-per-wave limit of seeding, 39 = its batched combine.
+// 37 / 38 = the shared-row scan's sample tiles and the tiles-per-wave limit of seeding, 39 = its batched combine,
+// 40 = its bf16 screen (0 = every (query, tile) pair folded).
 // Returns the previous value.
 int wvgx_set_tuning(int key, int value)
 {
@@ -584,6 +587,9 @@ int wvgx_set_tuning(int key, int value)
     } else if (key == 39) {
         old = t.qshare_combine;
         t.qshare_combine = value;
+    } else if (key == 40) {
+        old = t.qshare_screen;
+        t.qshare_screen = value;
     }
     return old;
 }

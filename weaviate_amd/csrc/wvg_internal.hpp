@@ -63,6 +63,7 @@ struct wvg_ctx {
     int num_cus = 256;
     wvg_options opt{};          // fixed at wvg_open / wvg_open_ex
     int order512 = 0;           // distancer kernels of an AMX + AVX-512 host (wvg_set_distance_order)
+    int qshare_screen = 1;      // the shared-row scan's bf16 screen (0 with WVG_QSHARE_SCREEN=0 at wvg_open)
     std::mutex pool_mu;
     std::vector<wvg::StreamSlot *> free_slots;
     std::vector<wvg::StreamSlot *> all_slots;
@@ -346,6 +347,11 @@ hipError_t launch_scan_f32_stream(const ScanArgs &a, const StreamJob &j, hipStre
 // the result's k-th key: the scan's lists start with tau = seed + 1 and a wave
 // sorts or inserts only the rows at or below the seed key, not the first k it
 // meets.  The host seeds where a wave has few tiles (qshare_seed_tiles).
+// Seeded L2 launches at d = 128 with k <= 64 are screened (qshare_screened):
+// the prologue also writes each query's bf16 image (qbf) and bound constants
+// (qconst), and scan_f32_qshare_screen_kernel folds a query on a tile only where
+// a bf16 MFMA lower bound of some live row's distance does not exceed the
+// query's tau.  Keys come from the exact chain only; results are unchanged.
 struct QShareArgs {
     const void *data;        // tiled corpus
     const uint64_t *valid;   // one word per tile
@@ -365,8 +371,14 @@ struct QShareArgs {
     uint64_t *seeds;         // [nq] sample k-th keys, written by the prologue
     uint32_t seed_tiles;     // tiles of the sample (0 = none: open bounds)
     uint32_t seq_combine;    // tools A/B: one group_combine_publish per query instead of the pass's batched combine
+    uint32_t screen;         // 1 = the screened scan (qshare_screened): the prologue writes qbf and qconst
+    uint16_t *qbf;           // [nq][128] the queries as bf16 (round to nearest), written by the prologue
+    float4 *qconst;          // [nq] {Nq2, K1q, K2q, Cq = Nq2 - K2q}: the screen's bound (wvg_qshare.hip)
+    uint64_t *screen_count;  // tools build: folded (low word) and all (high word) (query, tile) pairs of the launch
 };
 bool qshare_supported(int metric, uint32_t dim, int order512);
+// Whether a launch takes the screened form (L2, d = 128, k <= 64, seeded, Tuning::qshare_screen).
+bool qshare_screened(int metric, uint32_t dim, uint32_t k, uint32_t seed_tiles);
 uint32_t qshare_queries_per_pass(uint32_t dim, uint32_t k);
 uint32_t qshare_groups(uint64_t ntiles, int num_cus);
 // Tiles of the prologue's sample for a scan of ntiles tiles by `groups` workgroups (0 = no seeding).
@@ -604,6 +616,9 @@ struct Tuning {
                                 // (+29 % at 8, +10 % at 30, +4 % at 122 tiles per wave, the largest measured)
     int qshare_combine = 1;  // (tuning key 39) 1 = the pass's lists combined in one step, every wave merging its
                              // share of the queries; 0 = one group_combine_publish per query on wave 0 (A/B)
+    int qshare_screen = 1;   // (tuning key 40) 1 = seeded L2 d = 128 k <= 64 launches screen every tile with a bf16
+                             // MFMA lower bound and fold only the admitted (query, tile) pairs; 0 = every pair
+                             // folded (A/B; profiles/r12/qshare_screen/)
     int multi_bq_bound = 1;  // multi-GPU BQ heap flow (tuning key 36): 1 = the cross-slab bound X_s in the filter,
                              // 0 = every slab filters with its own thresholds only (A/B: rows replayed)
     int screen_diag = 0;     // K3c diagnostics (tools build only; results are NOT distances): bit 0 = no

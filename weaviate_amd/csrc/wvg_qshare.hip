@@ -27,6 +27,52 @@
 // mergers.  qshare_seed_kernel (launched before the scan, in place of the
 // memset of the ready words) scores a sample of the first tiles and leaves the
 // sample's k-th key per query; the lists start from that bound (QShareArgs).
+//
+// The screen (scan_f32_qshare_screen_kernel: L2, d = 128, k <= 64, seeded
+// launches).  With the seed bound nearly every exact distance is computed only
+// to be rejected by one compare.  So per tile a bf16 MFMA dot of every row with
+// every query of the pass gives a rigorous lower bound of the exact distance,
+// and a query is folded on the tile (today's code for all 64 lanes, unchanged)
+// only if some live row's lower bound does not exceed the query's tau.  A
+// skipped (query, tile) holds no key below tau -- offer_bounded would have
+// returned at its first ballot -- so every list is the unscreened one after
+// every tile, and only the exact chain produces keys.
+//
+// The bound.  u = 2^-24, d = 128, q and x the fp32 vectors, D = |q - x|^2 =
+// |q|^2 + |x|^2 - 2 q.x in real numbers, r = the exact chain's fp32 result.
+//  (a) r >= D (1 - (d + 4) u) - 2^-109: every term of r is non-negative and
+//      passes at most 2 (the subtraction, squared) + d / 8 (its chain's fmas)
+//      + 5 (avx256_reduce) roundings; underflowing fmas lose at most d 2^-126.
+//      D <= 2 (|q|^2 + |x|^2), so the loss is at most 2 (d + 4) u (|q|^2 + |x|^2).
+//  (b) m = the MFMA dot of bf16(q), bf16(x) (round to nearest, |v - bf16(v)| <=
+//      2^-8 |v|, products exact in fp32, fp32 accumulation): K3c's bound
+//      (wvg_screen.hip) |q.x - m| <= c |q| |x| + (denormal terms), c = 2^-7 +
+//      2^-15 + d 2^-21, by Cauchy-Schwarz.
+//  (c) Nq2 = |q|^2 and Nq >= |q| come from a double sum in the prologue.  Nx2 is
+//      the lane's fp32 sum of x_i^2 in any order: |x|^2 >= Nx2 (1 - d u), and
+//      |x|^2 <= Nx2 (1 + d u) + d 2^-126 (squares below 2^-126 may vanish), so
+//      with Nx = sqrt(Nx2) (1 + 2^-16) (v_sqrt_f32 is within 1 ulp and may flush
+//      a denormal Nx2): |x| <= Nx + eta, eta = 2^-59.
+//  (d) the combine runs in fp32: Bx = Nx2 (1 - g), t = Bx + Cq, t = fma(-2, m, t),
+//      lower = fma(-K1q, Nx, t); each rounding is at most u times a value below
+//      2.2 (Nq2 + Nx2).
+// (a), (c) and (d) together cost less than 400 u (Nq2 + Nx2); g = 2^-15 = 512 u
+// pays for them.  (b) with (c) costs 2 c (Nq Nx + eta (Nq + Nx) + eta^2) plus
+// 2^-119 (Nq + Nx) + 2^-109 for bf16 operands and products that flush.  Hence
+//   lower = (Nq2 + Nx2 - 2 m) - (K1q Nx + K2q + g Nx2) <= r,
+//   K1q = (2 c Nq + 2^-60) (1 + 2^-20),  K2q = g Nq2 + 2^-60 Nq + 2^-100,
+// the form lower = (Nq2 + Nx2 - 2m) - (K1q Nx + K2q (1 + Nx2)) with the second
+// term's Nq2 kept apart from Nx2 (g (Nq2 + Nx2) instead of g max(1, Nq2) (1 +
+// Nx2): the same bound for small norms, a useful one for large norms).  The
+// prologue stores Cq = Nq2 - K2q.  Special values: a NaN or an infinity in q, x,
+// the norms, m (bf16 or fp32 overflow included) makes lower NaN or infinite, and
+// the tile is skipped only if lower > tau_dist AND lower < +inf: anything
+// else folds.  tau_dist is the float under tau's high word (NaN for an open tau:
+// folds); lower > tau_dist gives ord(r) > ord(tau_dist), so no key below tau.
+// The operands: v_mfma_f32_4x4x4_16b_bf16 is 16 independent 4x4x4 blocks, block
+// = lane / 4.  B = 4 k-values of the lane's own row; A = the same 4 k-values of
+// query 4 g + (lane & 3) from the LDS image; result register i of the lane = its
+// row's dot with query 4 g + i.
 #include <algorithm>
 
 #include "wvg_internal.hpp"
@@ -96,6 +142,44 @@ __device__ __forceinline__ uint64_t seed_bound(cu64 *seed)
     return s + (s != WVG_KEY_NONE ? 1ull : 0ull);
 }
 
+// The screen's constants (the bound at the top of the file) and operand types.
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef short shortx4 __attribute__((ext_vector_type(4)));
+constexpr int QS_D = 128;                   // the screened form's dimension
+constexpr double QS_C = 0x1p-7 + 0x1p-15 + QS_D * 0x1p-21;
+constexpr float QS_G = 0x1p-15f;
+constexpr int QS_QROW = QS_D * 2 / 16 + 1;  // uint4 per query of the LDS image: 256 B + 16 B (the four
+                                            // queries a ds_read_b128 fetches then lie in different banks)
+
+__device__ __forceinline__ shortx4 bf16_of(float4 x)  // two v_cvt_pk_bf16_f32: round to nearest even
+{
+    const bf16x2 lo = __builtin_convertvector(f2v{x.x, x.y}, bf16x2), hi = __builtin_convertvector(f2v{x.z, x.w}, bf16x2);
+    return __builtin_bit_cast(shortx4, make_uint2(__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi)));
+}
+
+// The query side of the screen, by one wave: the query's bf16 image and
+// {Nq2, K1q, K2q, Cq = Nq2 - K2q} from the double square sum.  A non-finite
+// query ends in NaN or infinite constants (Cq = inf - inf), which fold.
+__device__ __forceinline__ void screen_query_side(const QShareArgs &a, uint32_t q, cf4 *qj, int lane)
+{
+    const int c = lane & (QS_D / 4 - 1);
+    const f4v v = qj[c];
+    double ss = lane < QS_D / 4
+                    ? (double)v.x * (double)v.x + (double)v.y * (double)v.y + (double)v.z * (double)v.z + (double)v.w * (double)v.w
+                    : 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    if (lane < QS_D / 4)
+        reinterpret_cast<shortx4 *>(a.qbf)[(size_t)q * (QS_D / 4) + c] = bf16_of(make_float4(v.x, v.y, v.z, v.w));
+    if (lane == 0) {
+        const double nq = __builtin_sqrt(ss) * (1.0 + 1e-6);
+        const double k1 = (2.0 * QS_C * nq + 0x1p-60) * (1.0 + 0x1p-20);
+        const double k2 = (double)QS_G * ss + 0x1p-60 * nq + 0x1p-100;
+        a.qconst[q] = make_float4((float)ss, (float)k1, (float)k2, (float)(ss - k2));
+    }
+}
+
 // The prologue of a shared-row launch.  The grid zeroes the ready words; then
 // workgroup q scores the first a.seed_tiles tiles of the range for query q -- a
 // wave the tiles wave, wave + SEED_WAVES, ..., with the scan's validity words
@@ -112,16 +196,24 @@ __global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nready; i += (uint64_t)gridDim.x * blockDim.x)
         a.ready[i] = 0u;
     const uint32_t q = blockIdx.x;  // gridDim.x == nq
+    const int lane = threadIdx.x & 63, wave = wave_id();
+    cf4 *qj = (cf4 *)a.queries + (size_t)q * (a.qpitch / 4);
+    if constexpr (METRIC == WVG_M_L2 && D == QS_D) {
+        if (a.screen) {  // the scan screens: its query side, by the last wave (it has the fewest sample tiles)
+#ifdef WVG_TOOLS
+            if (threadIdx.x == 0 && q == 0) *a.screen_count = 0ull;
+#endif
+            if (wave == SEED_WAVES - 1) screen_query_side(a, q, qj, lane);
+        }
+    }
     const uint64_t ntiles = a.tile_end - a.tile_begin;
     const uint64_t ns = a.seed_tiles < ntiles ? a.seed_tiles : ntiles;
     if (ns == 0) {  // workgroup-uniform
         if (threadIdx.x == 0) a.seeds[q] = WVG_KEY_NONE;
         return;
     }
-    const int lane = threadIdx.x & 63, wave = wave_id();
     const float4 *data = reinterpret_cast<const float4 *>(a.data);
     cu64 *valid = (cu64 *)a.valid;
-    cf4 *qj = (cf4 *)a.queries + (size_t)q * (a.qpitch / 4);
     WaveTopK<E> tk;
     tk.init((int)a.k);
     for (uint64_t t = a.tile_begin + (uint64_t)wave; t < a.tile_begin + ns; t += SEED_WAVES) {
@@ -152,12 +244,15 @@ __global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs
 // each as group_combine_publish does (write-through stores, the storing wave's
 // own drain, then the list's ready word).  Keys are unique, so the merge order
 // does not change a list.
-template <int E, int QP>
+// FRESH: the lane's addresses are formed here and not held in registers through
+// the scan (the screened form has none to spare).
+template <int E, int QP, bool FRESH = false>
 __device__ __forceinline__ void pass_combine_publish(WaveTopK<E> (&tk)[QP], uint32_t nqp, uint32_t k, uint64_t *partials,
                                                      uint32_t *ready, size_t list0, uint32_t G, bool more)
 {
     __shared__ uint64_t psh[QP][SCAN_WAVES][64 * E];
-    const int lane = threadIdx.x & 63;
+    int lane = threadIdx.x & 63;
+    if constexpr (FRESH) asm volatile("" : "+v"(lane));
     const int wave = wave_id();
 #pragma unroll
     for (int j = 0; j < QP; j++)
@@ -188,12 +283,65 @@ __device__ __forceinline__ void pass_combine_publish(WaveTopK<E> (&tk)[QP], uint
     if (more) __syncthreads();  // psh is reused by the next pass
 }
 
-// (two waves per SIMD -- at most 256 registers -- so one wave's tile loads run under the other's folds)
-template <int METRIC, int D, int E, bool WHOLE>
-__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_kernel(
-    QShareArgs a)
+// The screen of one tile (the bound at the top of the file): the queries of the
+// pass that must be folded on it, as a wave-uniform mask.  xs = the lane's row,
+// qsh = the pass's bf16 queries (QS_QROW uint4 each), kq = their {Nq2, K1q, K2q,
+// Cq}, m = the tile's validity word.  32 k-steps x 4 query groups of MFMAs; a
+// ds_read_b128 per group feeds two k-steps.
+template <int QP>
+__device__ __forceinline__ uint32_t screen_tile(const float4 (&xs)[QS_D / 4], const uint4 *qsh, cf4 *kq,
+                                                const WaveTopK<1> (&tk)[QP], uint32_t nqp, uint64_t m, int lane)
+{
+    static_assert(QP == 16, "four query groups of four");
+    f2v n2a = {0.0f, 0.0f}, n2b = {0.0f, 0.0f};
+    floatx4 acc[4];
+#pragma unroll
+    for (int g = 0; g < 4; g++) acc[g] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+    const uint4 *ql = qsh + (lane & 3) * QS_QROW;
+#pragma unroll
+    for (int c = 0; c < QS_D / 4; c += 2) {
+        uint4 aq[4];
+#pragma unroll
+        for (int g = 0; g < 4; g++) aq[g] = ql[g * 4 * QS_QROW + c / 2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const float4 x = xs[c + h];
+            const f2v xlo = {x.x, x.y}, xhi = {x.z, x.w};
+            n2a = __builtin_elementwise_fma(xlo, xlo, n2a);
+            n2b = __builtin_elementwise_fma(xhi, xhi, n2b);
+            const shortx4 b = bf16_of(x);
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const uint2 w = h ? make_uint2(aq[g].z, aq[g].w) : make_uint2(aq[g].x, aq[g].y);
+                acc[g] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(shortx4, w), b, acc[g], 0, 0, 0);
+            }
+        }
+    }
+    const f2v n2 = n2a + n2b;
+    const float nx2 = n2.x + n2.y;
+    const float nx = __builtin_amdgcn_sqrtf(nx2) * (1.0f + 0x1p-16f);
+    const float bx = nx2 * (1.0f - QS_G);
+    uint32_t fold = 0u;
+#pragma unroll
+    for (int j = 0; j < QP; j++) {
+        if ((uint32_t)j < nqp) {  // wave-uniform
+            const f4v k = kq[j];
+            const float t = __builtin_fmaf(-2.0f, acc[j >> 2][j & 3], bx + k.w);
+            const float lower = __builtin_fmaf(-k.y, nx, t);
+            const float tau_dist = wvg_unord_f32((uint32_t)(tk[j].tau >> 32));  // NaN for an open tau
+            const bool skip = lower > tau_dist && lower < __builtin_inff();
+            if ((__ballot(!skip) & m) != 0ull) fold |= 1u << j;
+        }
+    }
+    return fold;
+}
+
+// SCREEN: the bf16 screen per tile before the per-query folds (WHOLE, L2, d = 128, E = 1).
+template <int METRIC, int D, int E, bool WHOLE, bool SCREEN>
+__device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
 {
     static_assert(D % 32 == 0 && D > 0 && !is_abs_or_neq<METRIC>, "shared rows: fixed D, the AVX2 chains");
+    static_assert(!SCREEN || (WHOLE && METRIC == WVG_M_L2 && D == QS_D && E == 1), "the screened form");
     constexpr int QP = qshare_qp(D, E, WHOLE);
     constexpr int NC = D / 4;
     const uint32_t G = a.groups;
@@ -222,6 +370,11 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
     const float4 *data = reinterpret_cast<const float4 *>(a.data);
     cu64 *valid = (cu64 *)a.valid;
     const uint32_t qstride = a.qpitch / 4;
+    static_assert(!SCREEN || QP * 16 == SCAN_WAVES * 64, "the LDS image copy: one thread per (query, 16 bytes)");
+    __shared__ uint4 qsh[SCREEN ? QP * QS_QROW : 1];  // SCREEN: the pass's bf16 queries
+#ifdef WVG_TOOLS
+    uint32_t n_fold = 0, n_pairs = 0;  // SCREEN: folded and all (query, tile) pairs of this wave
+#endif
     for (uint32_t q0 = 0, pass = 0; q0 < a.nq; q0 += QP, pass++) {
         const uint32_t nqp = a.nq - q0 < (uint32_t)QP ? a.nq - q0 : (uint32_t)QP;  // queries of this pass
         const bool rev = ((a.reverse + pass) & 1u) != 0;  // serpentine over the passes
@@ -231,6 +384,14 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int j = 0; j < QP; j++) tk[j].init_bounded((int)a.k, (uint32_t)j < nqp ? seed_bound(sd + j) : WVG_KEY_NONE);
         cf4 *qb = (cf4 *)a.queries + (size_t)q0 * qstride;
+        if constexpr (SCREEN) {  // the pass's bf16 queries into LDS, thread = (query, 16 bytes); zero past nqp
+            uint32_t tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));  // the per-thread addresses are formed here, not held in registers through the scan
+            const uint32_t tq = tid >> 4, part = tid & 15;
+            const uint4 *src = reinterpret_cast<const uint4 *>(a.qbf) + (size_t)q0 * (QS_D * 2 / 16);
+            qsh[tq * QS_QROW + part] = tq < nqp ? src[tid] : make_uint4(0u, 0u, 0u, 0u);  // 16 parts per query
+            __syncthreads();  // (the last pass's readers are past pass_combine_publish's barriers)
+        }
         uint64_t m_next = n ? valid[rev ? t1 - 1 : t0] : 0ull;
         for (uint64_t i = 0; i < n; ++i) {
             const uint64_t t = rev ? t1 - 1 - i : t0 + i;
@@ -252,13 +413,27 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
                 // folded.  (The scheduler still gathers a query's loads at its start and parks some
                 // of the words in vector lanes: about one v_readlane per four packed operations.)
                 constexpr int NG = NC / 4;
+                uint32_t fold = 0u;  // SCREEN: the queries folded on this tile
+                if constexpr (SCREEN) {
+                    fold = screen_tile<QP>(xs, qsh, (cf4 *)a.qconst + q0, tk, nqp, m, lane);
+#ifdef WVG_TOOLS
+                    n_fold += (uint32_t)__builtin_popcount(fold);
+                    n_pairs += nqp;
+#endif
+                    if (fold == 0u) continue;  // wave-uniform
+                }
                 f4v qc[4], qn[4];
-                ld_granule(qc, qb);
+                ld_granule(qc, qb + (size_t)(SCREEN ? (uint32_t)__builtin_ctz(fold) : 0u) * qstride);
 #pragma unroll
                 for (int j = 0; j < QP; j++) {
-                    if ((uint32_t)j < nqp) {  // wave-uniform
+                    if (SCREEN ? ((fold >> j) & 1u) != 0u : (uint32_t)j < nqp) {  // wave-uniform
                         cf4 *qj = qb + (size_t)j * qstride;
-                        cf4 *qnext = qb + (size_t)((uint32_t)j + 1 < nqp ? j + 1 : j) * qstride;
+                        uint32_t jn = (uint32_t)j + 1 < nqp ? j + 1 : j;
+                        if constexpr (SCREEN) {  // the next folded query
+                            const uint32_t rest = fold & (0xFFFFFFFEu << j);
+                            jn = rest ? (uint32_t)__builtin_ctz(rest) : (uint32_t)j;
+                        }
+                        cf4 *qnext = qb + (size_t)jn * qstride;
                         f2v acc[4][4];
 #pragma unroll
                         for (int r = 0; r < 4; r++)
@@ -324,8 +499,28 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
             continue;
         }
 #endif
-        pass_combine_publish<E, QP>(tk, nqp, a.k, a.partials, a.ready, (size_t)q0 * G + blockIdx.x, G, q0 + QP < a.nq);
+        pass_combine_publish<E, QP, SCREEN>(tk, nqp, a.k, a.partials, a.ready, (size_t)q0 * G + blockIdx.x, G, q0 + QP < a.nq);
     }
+#ifdef WVG_TOOLS
+    if constexpr (SCREEN) {  // one add per wave: folded pairs in the low word, all pairs in the high word
+        if (lane == 0 && n_pairs) atomicAdd((unsigned long long *)a.screen_count, ((unsigned long long)n_pairs << 32) | n_fold);
+    }
+#endif
+}
+
+// (two waves per SIMD -- at most 256 registers -- so one wave's tile loads run under the other's folds)
+template <int METRIC, int D, int E, bool WHOLE>
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_kernel(
+    QShareArgs a)
+{
+    qshare_scan_body<METRIC, D, E, WHOLE, false>(a);
+}
+
+// The screened form: L2, d = 128, k <= 64, whole rows.
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_screen_kernel(
+    QShareArgs a)
+{
+    qshare_scan_body<WVG_M_L2, QS_D, 1, true, true>(a);
 }
 
 // Which corpora the kernel covers, its queries per pass and its grid.
@@ -369,6 +564,15 @@ uint32_t qshare_seed_tiles(uint32_t dim, uint64_t ntiles, uint32_t groups)
     return (uint32_t)std::min<uint64_t>((uint64_t)t.qshare_seed, ntiles);
 }
 
+// The screened form runs where seeding runs, for L2 with k <= 64 and whole rows:
+// dot / cosine, k > 64, d = 768 and unseeded shapes are at or near their memory
+// floor or start with open lists, where everything folds anyway.
+bool qshare_screened(int metric, uint32_t dim, uint32_t k, uint32_t seed_tiles)
+{
+    return tuning().qshare_screen != 0 && metric == WVG_M_L2 && dim == (uint32_t)QS_D && k <= 64 && seed_tiles > 0 &&
+           qshare_whole(dim);
+}
+
 template <int METRIC, int E>
 static hipError_t launch_seed_e(const QShareArgs &a, hipStream_t s)
 {
@@ -398,6 +602,11 @@ template <int METRIC, int E>
 static hipError_t launch_qshare_e(const QShareArgs &a, uint32_t mergers, hipStream_t s)
 {
     dim3 grid(a.groups + mergers), block(SCAN_WAVES * 64);
+    if (a.screen) {
+        if (METRIC != WVG_M_L2 || E != 1 || a.dim != QS_D || !a.qbf || !a.qconst) return hipErrorInvalidValue;
+        launch_timed(scan_f32_qshare_screen_kernel, grid, block, 0, s, a);
+        return hipGetLastError();
+    }
     if (a.dim == 128) {
 #ifdef WVG_TOOLS
         if (!qshare_whole(a.dim)) {

@@ -1287,9 +1287,11 @@ static StreamLayout stream_layout(const SearchPlan &p1, uint32_t nq, uint32_t k)
 
 // Workspace of the shared-row query stream (after the status block): partial
 // lists [nq][groups][k], the ready words [nq][groups] (zeroed per call by the
-// prologue launch), then the prologue's seeds [nq] (8 bytes each).
+// prologue launch), then the prologue's seeds [nq] (8 bytes each), the screen's
+// query side -- bf16 images [nq][128] (d = 128 only) and bound constants [nq]
+// (16 bytes each) -- and the tools build's screen counter.
 struct QShareLayout {
-    size_t partials = 0, ready = 0, seeds = 0, total = 0;
+    size_t partials = 0, ready = 0, seeds = 0, qbf = 0, qconst = 0, count = 0, total = 0;
     uint32_t groups = 0;
 };
 static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k)
@@ -1299,7 +1301,10 @@ static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uin
     l.partials = WS_STATUS_BYTES;
     l.ready = l.partials + align_up((size_t)nq * l.groups * k * 8, 256);
     l.seeds = l.ready + align_up((size_t)nq * l.groups * 4, 256);
-    l.total = l.seeds + align_up((size_t)nq * 8, 256);
+    l.qbf = l.seeds + align_up((size_t)nq * 8, 256);
+    l.qconst = l.qbf + (c->dim == 128 ? align_up((size_t)nq * 128 * 2, 256) : 0);
+    l.count = l.qconst + (c->dim == 128 ? align_up((size_t)nq * 16, 256) : 0);
+    l.total = l.count + 256;
     return l;
 }
 
@@ -1326,6 +1331,23 @@ size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
     const size_t shared = qshare_layout(c, p1, nq, kk).total;
     return std::max({dev, WS_STATUS_BYTES + chain, stream, shared});
 }
+
+#ifdef WVG_TOOLS
+// Tools build (not part of include/wvgpu.h): the screen counter of the last screened shared-row launch
+// of (c, nq, k) on this workspace: out2[0] = folded, out2[1] = all (query, tile) pairs.
+int wvgx_qshare_screen_counts(wvg_corpus *c, uint32_t nq, uint32_t k, void *d_workspace, void *stream, uint64_t *out2)
+{
+    if (!c || !d_workspace || !out2) return fail(WVG_ERR_INVALID, "null argument");
+    std::shared_lock<std::shared_mutex> lk(c->rw);
+    const QShareLayout l = qshare_layout(c, plan_search(c, 1, k, nullptr, 0), nq, k);
+    uint64_t v = 0;
+    WVG_HIP(hipMemcpyAsync(&v, (char *)d_workspace + l.count, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    WVG_HIP(hipStreamSynchronize((hipStream_t)stream));
+    out2[0] = v & 0xFFFFFFFFull;
+    out2[1] = v >> 32;
+    return WVG_OK;
+}
+#endif
 
 int wvg_search_device_check(wvg_ctx *ctx, void *d_workspace, void *stream)
 {
@@ -1393,6 +1415,12 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
         a.seeds = (uint64_t *)(w + l.seeds);
         a.seed_tiles = qshare_seed_tiles(c->dim, p.te - p.tb, l.groups);
         a.seq_combine = tuning().qshare_combine == 0;
+        a.screen = c->ctx->qshare_screen && qshare_screened(c->metric, c->dim, k, a.seed_tiles);
+        if (a.screen) {
+            a.qbf = (uint16_t *)(w + l.qbf);
+            a.qconst = (float4 *)(w + l.qconst);
+            a.screen_count = (uint64_t *)(w + l.count);
+        }
         WVG_HIP(launch_qshare_seed(a, s));  // zeroes the ready words, writes the seeds
         ProfArm arm(c->ctx);
         if (arm.rc) return arm.rc;

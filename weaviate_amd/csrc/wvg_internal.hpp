@@ -349,9 +349,13 @@ hipError_t launch_scan_f32_stream(const ScanArgs &a, const StreamJob &j, hipStre
 // meets.  The host seeds where a wave has few tiles (qshare_seed_tiles).
 // Seeded L2 launches at d = 128 with k <= 64 are screened (qshare_screened):
 // the prologue also writes each query's bf16 image (qbf) and bound constants
-// (qconst), and scan_f32_qshare_screen_kernel folds a query on a tile only where
-// a bf16 MFMA lower bound of some live row's distance does not exceed the
-// query's tau.  Keys come from the exact chain only; results are unchanged.
+// (qconst), and scan_f32_qshare_screen_kernel runs the exact chain only for the
+// (query, row) pairs whose bf16 MFMA lower bound does not exceed the query's
+// tau: per tile every lane gets a mask of its row's admitted queries and scores
+// one of them per round, the fp32 queries read from LDS.  Keys come from the
+// exact chain only; results are unchanged.  (The tile-level fold before it ran
+// the chain for all 64 rows of 33.6 % of the (query, tile) pairs at about 260
+// VALU instructions each, beside a screen epilogue of about 13 per query.)
 struct QShareArgs {
     const void *data;        // tiled corpus
     const uint64_t *valid;   // one word per tile
@@ -374,7 +378,9 @@ struct QShareArgs {
     uint32_t screen;         // 1 = the screened scan (qshare_screened): the prologue writes qbf and qconst
     uint16_t *qbf;           // [nq][128] the queries as bf16 (round to nearest), written by the prologue
     float4 *qconst;          // [nq] {Nq2, K1q, K2q, Cq = Nq2 - K2q}: the screen's bound (wvg_qshare.hip)
-    uint64_t *screen_count;  // tools build: folded (low word) and all (high word) (query, tile) pairs of the launch
+    uint64_t *screen_count;  // tools build, two words per launch: [0] (query, tile) pairs with an admitted row (low
+                             // half) and all (query, tile) pairs (high half); [1] admitted (query, row) pairs (low
+                             // half) and rounds of the exact chain (high half)
 };
 bool qshare_supported(int metric, uint32_t dim, int order512);
 // Whether a launch takes the screened form (L2, d = 128, k <= 64, seeded, Tuning::qshare_screen).

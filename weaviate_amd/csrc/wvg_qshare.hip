@@ -32,11 +32,35 @@
 // launches).  With the seed bound nearly every exact distance is computed only
 // to be rejected by one compare.  So per tile a bf16 MFMA dot of every row with
 // every query of the pass gives a rigorous lower bound of the exact distance,
-// and a query is folded on the tile (today's code for all 64 lanes, unchanged)
-// only if some live row's lower bound does not exceed the query's tau.  A
-// skipped (query, tile) holds no key below tau -- offer_bounded would have
-// returned at its first ballot -- so every list is the unscreened one after
-// every tile, and only the exact chain produces keys.
+// and the exact chain runs only for the (query, row) pairs whose lower bound
+// does not exceed the query's tau: the screen leaves every lane a mask of its
+// row's admitted queries.  A pair that is not admitted holds no key below tau --
+// offer_bounded would have dropped it at its first ballot -- so every list is
+// the unscreened one after every tile, and only the exact chain produces keys.
+//
+// The rounds.  While any lane of the tile has a bit set, each lane takes its
+// lowest admitted query jl, clears the bit and runs the unchanged chain on its
+// own row (chunk_update2 in chunk order, avx256_reduce2, wrap_metric, lane_key:
+// the same lane-wise instructions on the same operands, hence the same bits),
+// the query chunks read from an fp32 LDS image of the pass's queries at its own
+// jl (QS_FROW pads a query to 528 B so that lanes reading different queries at
+// one chunk do not meet in one bank).  Then, for every query j that some lane
+// took (an unrolled loop with a wave-uniform test: tk[] is never indexed
+// dynamically), the lanes with jl = j offer their keys to tk[j] and the others
+// offer KEY_NONE.  A query may so be offered in more than one round of a tile,
+// and in an order that differs from lane to lane.  That changes no list: a list
+// is the set of the k smallest unique keys below its bound among the keys
+// offered so far, whatever the batches they came in (offer_bounded inserts or
+// merges exactly the keys below tau, and tau only falls), and a pair admitted
+// under an earlier, larger tau of the same tile is merely offered and dropped.
+// So after each tile every list equals the one the tile-level fold left.  A NaN
+// or infinite lower bound or an open tau sets the bit: a lane holding a NaN row
+// runs up to 16 rounds, and a pass with open seeds runs 16 full rounds per tile,
+// the unscreened cost.  On the bench's shape (1M x 128 uniform rows, k = 10, 16
+// queries) 0.6 % of the pairs are admitted -- about 6 of a tile's 1,024 -- and a
+// tile needs about 1.5 rounds, where the tile-level fold ran about 5.4 chains of
+// 64 rows per tile (33.6 % of the (query, tile) pairs) at about 260 VALU
+// instructions each; the screen's own epilogue is about 13 per query.
 //
 // The bound.  u = 2^-24, d = 128, q and x the fp32 vectors, D = |q - x|^2 =
 // |q|^2 + |x|^2 - 2 q.x in real numbers, r = the exact chain's fp32 result.
@@ -66,9 +90,9 @@
 // Nx2): the same bound for small norms, a useful one for large norms).  The
 // prologue stores Cq = Nq2 - K2q.  Special values: a NaN or an infinity in q, x,
 // the norms, m (bf16 or fp32 overflow included) makes lower NaN or infinite, and
-// the tile is skipped only if lower > tau_dist AND lower < +inf: anything
-// else folds.  tau_dist is the float under tau's high word (NaN for an open tau:
-// folds); lower > tau_dist gives ord(r) > ord(tau_dist), so no key below tau.
+// the pair is skipped only if lower > tau_dist AND lower < +inf: anything
+// else is admitted.  tau_dist is the float under tau's high word (NaN for an open
+// tau: admitted); lower > tau_dist gives ord(r) > ord(tau_dist), so no key below tau.
 // The operands: v_mfma_f32_4x4x4_16b_bf16 is 16 independent 4x4x4 blocks, block
 // = lane / 4.  B = 4 k-values of the lane's own row; A = the same 4 k-values of
 // query 4 g + (lane & 3) from the LDS image; result register i of the lane = its
@@ -151,6 +175,8 @@ constexpr double QS_C = 0x1p-7 + 0x1p-15 + QS_D * 0x1p-21;
 constexpr float QS_G = 0x1p-15f;
 constexpr int QS_QROW = QS_D * 2 / 16 + 1;  // uint4 per query of the LDS image: 256 B + 16 B (the four
                                             // queries a ds_read_b128 fetches then lie in different banks)
+constexpr int QS_FROW = QS_D / 4 + 1;       // f4v per query of the fp32 LDS image: 512 B + 16 B (lanes that read
+                                            // different queries at one chunk then lie in different banks)
 
 __device__ __forceinline__ shortx4 bf16_of(float4 x)  // two v_cvt_pk_bf16_f32: round to nearest even
 {
@@ -201,7 +227,7 @@ __global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs
     if constexpr (METRIC == WVG_M_L2 && D == QS_D) {
         if (a.screen) {  // the scan screens: its query side, by the last wave (it has the fewest sample tiles)
 #ifdef WVG_TOOLS
-            if (threadIdx.x == 0 && q == 0) *a.screen_count = 0ull;
+            if (threadIdx.x == 0 && q == 0) a.screen_count[0] = a.screen_count[1] = 0ull;
 #endif
             if (wave == SEED_WAVES - 1) screen_query_side(a, q, qj, lane);
         }
@@ -283,11 +309,12 @@ __device__ __forceinline__ void pass_combine_publish(WaveTopK<E> (&tk)[QP], uint
     if (more) __syncthreads();  // psh is reused by the next pass
 }
 
-// The screen of one tile (the bound at the top of the file): the queries of the
-// pass that must be folded on it, as a wave-uniform mask.  xs = the lane's row,
-// qsh = the pass's bf16 queries (QS_QROW uint4 each), kq = their {Nq2, K1q, K2q,
-// Cq}, m = the tile's validity word.  32 k-steps x 4 query groups of MFMAs; a
-// ds_read_b128 per group feeds two k-steps.
+// The screen of one tile (the bound at the top of the file): per lane, the
+// queries of the pass that must be scored exactly on the lane's row (bit j =
+// query j; 0 for a dead lane).  xs = the lane's row, qsh = the pass's bf16
+// queries (QS_QROW uint4 each), kq = their {Nq2, K1q, K2q, Cq}, m = the tile's
+// validity word.  32 k-steps x 4 query groups of MFMAs; a ds_read_b128 per group
+// feeds two k-steps.
 template <int QP>
 __device__ __forceinline__ uint32_t screen_tile(const float4 (&xs)[QS_D / 4], const uint4 *qsh, cf4 *kq,
                                                 const WaveTopK<1> (&tk)[QP], uint32_t nqp, uint64_t m, int lane)
@@ -321,7 +348,7 @@ __device__ __forceinline__ uint32_t screen_tile(const float4 (&xs)[QS_D / 4], co
     const float nx2 = n2.x + n2.y;
     const float nx = __builtin_amdgcn_sqrtf(nx2) * (1.0f + 0x1p-16f);
     const float bx = nx2 * (1.0f - QS_G);
-    uint32_t fold = 0u;
+    uint32_t adm = 0u;
 #pragma unroll
     for (int j = 0; j < QP; j++) {
         if ((uint32_t)j < nqp) {  // wave-uniform
@@ -330,13 +357,13 @@ __device__ __forceinline__ uint32_t screen_tile(const float4 (&xs)[QS_D / 4], co
             const float lower = __builtin_fmaf(-k.y, nx, t);
             const float tau_dist = wvg_unord_f32((uint32_t)(tk[j].tau >> 32));  // NaN for an open tau
             const bool skip = lower > tau_dist && lower < __builtin_inff();
-            if ((__ballot(!skip) & m) != 0ull) fold |= 1u << j;
+            adm |= skip ? 0u : 1u << j;
         }
     }
-    return fold;
+    return ((m >> lane) & 1ull) ? adm : 0u;
 }
 
-// SCREEN: the bf16 screen per tile before the per-query folds (WHOLE, L2, d = 128, E = 1).
+// SCREEN: the bf16 screen per tile, then rounds of the exact chain per admitted row (WHOLE, L2, d = 128, E = 1).
 template <int METRIC, int D, int E, bool WHOLE, bool SCREEN>
 __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
 {
@@ -372,8 +399,11 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
     const uint32_t qstride = a.qpitch / 4;
     static_assert(!SCREEN || QP * 16 == SCAN_WAVES * 64, "the LDS image copy: one thread per (query, 16 bytes)");
     __shared__ uint4 qsh[SCREEN ? QP * QS_QROW : 1];  // SCREEN: the pass's bf16 queries
+    __shared__ f4v qfsh[SCREEN ? QP * QS_FROW : 1];   // SCREEN: the pass's fp32 queries (the rounds' operands)
 #ifdef WVG_TOOLS
-    uint32_t n_fold = 0, n_pairs = 0;  // SCREEN: folded and all (query, tile) pairs of this wave
+    // SCREEN, of this wave: (query, tile) pairs with an admitted row, all (query, tile) pairs, rounds;
+    // of this lane: admitted (query, row) pairs
+    uint32_t n_fold = 0, n_pairs = 0, n_rounds = 0, n_adm = 0;
 #endif
     for (uint32_t q0 = 0, pass = 0; q0 < a.nq; q0 += QP, pass++) {
         const uint32_t nqp = a.nq - q0 < (uint32_t)QP ? a.nq - q0 : (uint32_t)QP;  // queries of this pass
@@ -390,6 +420,13 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
             const uint32_t tq = tid >> 4, part = tid & 15;
             const uint4 *src = reinterpret_cast<const uint4 *>(a.qbf) + (size_t)q0 * (QS_D * 2 / 16);
             qsh[tq * QS_QROW + part] = tq < nqp ? src[tid] : make_uint4(0u, 0u, 0u, 0u);  // 16 parts per query
+            // and the fp32 queries, two chunks per thread: thread = (query, chunk), (query + QP / 2, chunk)
+            const f4v *srcf = reinterpret_cast<const f4v *>(a.queries) + (size_t)q0 * qstride;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const uint32_t fq = (tid >> 5) + h * (QP / 2), fc = tid & 31;
+                qfsh[fq * QS_FROW + fc] = fq < nqp ? srcf[(size_t)fq * qstride + fc] : f4v{0.0f, 0.0f, 0.0f, 0.0f};
+            }
             __syncthreads();  // (the last pass's readers are past pass_combine_publish's barriers)
         }
         uint64_t m_next = n ? valid[rev ? t1 - 1 : t0] : 0ull;
@@ -408,47 +445,78 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
 #pragma unroll
                     for (int c = 0; c < NC; c++) xs[c] = ld_stream<true>(rp + (size_t)c * 64);
                 }
-                // The query words come 16 floats (a granule = one scalar load) at a time, the next
-                // granule -- at a query's end the next query's first -- requested before this one is
-                // folded.  (The scheduler still gathers a query's loads at its start and parks some
-                // of the words in vector lanes: about one v_readlane per four packed operations.)
-                constexpr int NG = NC / 4;
-                uint32_t fold = 0u;  // SCREEN: the queries folded on this tile
                 if constexpr (SCREEN) {
-                    fold = screen_tile<QP>(xs, qsh, (cf4 *)a.qconst + q0, tk, nqp, m, lane);
+                    // Row-level admission: the lane's mask of queries whose lower bound on its row does
+                    // not exceed tau, then rounds of the exact chain -- a lane scores its own row against
+                    // one of its own admitted queries per round, the query chunks read from LDS.
+                    uint32_t adm = screen_tile<QP>(xs, qsh, (cf4 *)a.qconst + q0, tk, nqp, m, lane);
 #ifdef WVG_TOOLS
-                    n_fold += (uint32_t)__builtin_popcount(fold);
                     n_pairs += nqp;
-#endif
-                    if (fold == 0u) continue;  // wave-uniform
-                }
-                f4v qc[4], qn[4];
-                ld_granule(qc, qb + (size_t)(SCREEN ? (uint32_t)__builtin_ctz(fold) : 0u) * qstride);
+                    n_adm += (uint32_t)__builtin_popcount(adm);
+                    {
+                        uint32_t any = 0u;
 #pragma unroll
-                for (int j = 0; j < QP; j++) {
-                    if (SCREEN ? ((fold >> j) & 1u) != 0u : (uint32_t)j < nqp) {  // wave-uniform
-                        cf4 *qj = qb + (size_t)j * qstride;
-                        uint32_t jn = (uint32_t)j + 1 < nqp ? j + 1 : j;
-                        if constexpr (SCREEN) {  // the next folded query
-                            const uint32_t rest = fold & (0xFFFFFFFEu << j);
-                            jn = rest ? (uint32_t)__builtin_ctz(rest) : (uint32_t)j;
-                        }
-                        cf4 *qnext = qb + (size_t)jn * qstride;
+                        for (int j = 0; j < QP; j++) any |= __ballot(((adm >> j) & 1u) != 0u) != 0ull ? 1u << j : 0u;
+                        n_fold += (uint32_t)__builtin_popcount(any);
+                    }
+#endif
+                    while (true) {
+                        const uint64_t took_any = __ballot(adm != 0u);  // the lanes that score a pair in this round
+                        if (took_any == 0ull) break;  // wave-uniform
+#ifdef WVG_TOOLS
+                        n_rounds++;
+#endif
+                        const bool has = adm != 0u;
+                        const uint32_t jl = has ? (uint32_t)__builtin_ctz(adm) : 0u;  // the lane's lowest admitted query
+                        adm &= adm - 1u;
+                        const f4v *ql = qfsh + jl * QS_FROW;
                         f2v acc[4][4];
 #pragma unroll
                         for (int r = 0; r < 4; r++)
 #pragma unroll
                             for (int p = 0; p < 4; p++) acc[r][p] = f2v{0.0f, 0.0f};
+                        // (a read-ahead of two or four chunks written out here spills: the kernel sits at 255 registers)
 #pragma unroll
-                        for (int g = 0; g < NG; g++) {
-                            ld_granule(qn, g + 1 < NG ? qj + (g + 1) * 4 : qnext);
+                        for (int c = 0; c < NC; c++) chunk_update2<METRIC>(acc, c & 7, ql[c], xs[c]);
+                        const uint64_t key = lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane);
 #pragma unroll
-                            for (int c = 0; c < 4; c++) chunk_update2<METRIC>(acc, (g * 4 + c) & 7, qc[c], xs[g * 4 + c]);
-#pragma unroll
-                            for (int c = 0; c < 4; c++) qc[c] = qn[c];
+                        for (int j = 0; j < QP; j++) {
+                            const uint64_t took = __ballot(jl == (uint32_t)j) & took_any;
+                            if (took != 0ull)  // wave-uniform: some lane took query j in this round
+                                tk[j].offer_bounded(((took >> lane) & 1ull) ? key : WVG_KEY_NONE,
+                                                    [&] { return seed_bound(sd + j); });
                         }
-                        tk[j].offer_bounded(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane),
-                                            [&] { return seed_bound(sd + j); });
+                    }
+                } else {
+                    // The query words come 16 floats (a granule = one scalar load) at a time, the next
+                    // granule -- at a query's end the next query's first -- requested before this one is
+                    // folded.  (The scheduler still gathers a query's loads at its start and parks some
+                    // of the words in vector lanes: about one v_readlane per four packed operations.)
+                    constexpr int NG = NC / 4;
+                    f4v qc[4], qn[4];
+                    ld_granule(qc, qb);
+#pragma unroll
+                    for (int j = 0; j < QP; j++) {
+                        if ((uint32_t)j < nqp) {  // wave-uniform
+                            cf4 *qj = qb + (size_t)j * qstride;
+                            const uint32_t jn = (uint32_t)j + 1 < nqp ? j + 1 : j;
+                            cf4 *qnext = qb + (size_t)jn * qstride;
+                            f2v acc[4][4];
+#pragma unroll
+                            for (int r = 0; r < 4; r++)
+#pragma unroll
+                                for (int p = 0; p < 4; p++) acc[r][p] = f2v{0.0f, 0.0f};
+#pragma unroll
+                            for (int g = 0; g < NG; g++) {
+                                ld_granule(qn, g + 1 < NG ? qj + (g + 1) * 4 : qnext);
+#pragma unroll
+                                for (int c = 0; c < 4; c++) chunk_update2<METRIC>(acc, (g * 4 + c) & 7, qc[c], xs[g * 4 + c]);
+#pragma unroll
+                                for (int c = 0; c < 4; c++) qc[c] = qn[c];
+                            }
+                            tk[j].offer_bounded(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane),
+                                                [&] { return seed_bound(sd + j); });
+                        }
                     }
                 }
             } else {
@@ -502,8 +570,15 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
         pass_combine_publish<E, QP, SCREEN>(tk, nqp, a.k, a.partials, a.ready, (size_t)q0 * G + blockIdx.x, G, q0 + QP < a.nq);
     }
 #ifdef WVG_TOOLS
-    if constexpr (SCREEN) {  // one add per wave: folded pairs in the low word, all pairs in the high word
-        if (lane == 0 && n_pairs) atomicAdd((unsigned long long *)a.screen_count, ((unsigned long long)n_pairs << 32) | n_fold);
+    if constexpr (SCREEN) {  // two adds per wave: word 0 = (query, tile) pairs with an admitted row (low half)
+                             // and all (query, tile) pairs (high half); word 1 = admitted (query, row) pairs
+                             // (low half) and rounds (high half)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) n_adm += __shfl_xor(n_adm, off);
+        if (lane == 0 && n_pairs) {
+            atomicAdd((unsigned long long *)a.screen_count, ((unsigned long long)n_pairs << 32) | n_fold);
+            atomicAdd((unsigned long long *)a.screen_count + 1, ((unsigned long long)n_rounds << 32) | n_adm);
+        }
     }
 #endif
 }

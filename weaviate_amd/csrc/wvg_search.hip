@@ -1347,6 +1347,21 @@ int wvgx_qshare_screen_counts(wvg_corpus *c, uint32_t nq, uint32_t k, void *d_wo
     out2[1] = v >> 32;
     return WVG_OK;
 }
+
+// The counter block's second word, same launch: out2[0] = admitted (query, row) pairs, out2[1] = rounds of the
+// exact chain (one per wave and round).
+int wvgx_qshare_row_counts(wvg_corpus *c, uint32_t nq, uint32_t k, void *d_workspace, void *stream, uint64_t *out2)
+{
+    if (!c || !d_workspace || !out2) return fail(WVG_ERR_INVALID, "null argument");
+    std::shared_lock<std::shared_mutex> lk(c->rw);
+    const QShareLayout l = qshare_layout(c, plan_search(c, 1, k, nullptr, 0), nq, k);
+    uint64_t v = 0;
+    WVG_HIP(hipMemcpyAsync(&v, (char *)d_workspace + l.count + 8, 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    WVG_HIP(hipStreamSynchronize((hipStream_t)stream));
+    out2[0] = v & 0xFFFFFFFFull;
+    out2[1] = v >> 32;
+    return WVG_OK;
+}
 #endif
 
 int wvg_search_device_check(wvg_ctx *ctx, void *d_workspace, void *stream)

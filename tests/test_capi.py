@@ -125,9 +125,9 @@ def test_hot_kernels_use_no_scratch(tmp_path):
     readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
     if not os.path.exists(readelf):
         pytest.skip("llvm-readelf not available")
-    hot = ("scan_f32_stream_kernel", "scan_f32_kernel", "screen_ar_kernel", "screen_kernel", "scan_pq32_wide_kernel",
-           "scan_pq32_rot_kernel", "scan_bq_kernel", "gemm_rs_kernel", "pq_encode_kernel", "merge_keys_kernel",
-           "scan_f32_mq_kernel", "emit_prefix_kernel", "emit_filter_kernel", "emit_gather_kernel")
+    hot = ("scan_f32_stream_kernel", "scan_f32_kernel", "screen_ar_kernel", "screen_i8_kernel", "screen_kernel",
+           "scan_pq32_wide_kernel", "scan_pq32_rot_kernel", "scan_bq_kernel", "gemm_rs_kernel", "pq_encode_kernel",
+           "merge_keys_kernel", "scan_f32_mq_kernel", "emit_prefix_kernel", "emit_filter_kernel", "emit_gather_kernel")
     bad, seen = [], 0
     for j, co in enumerate(_gfx950_code_objects(_lib.LIB_PATH)):
         f = tmp_path / f"co{j}.o"
@@ -198,3 +198,43 @@ def test_k1_matrix_covers_every_specialization(tmp_path):
     for fam in K1_FAMILIES:  # every family in every list size and metric kernel (K1Q: L2 / dot only)
         assert {a[0] for f, a in found if f == fam} == ({0, 1} if fam == "scan_f32_mq_kernel" else {0, 1, 3, 4}), fam
         assert {a[2] for f, a in found if f == fam} == {1, 2, 4}, fam
+
+
+def _screen_instantiations(lib_path, tmp_path, readelf):
+    """{(kernel, (template arguments...))} of the batched screen's scoring kernels -- every
+    kernel that takes a ScreenArgs -- in the library's gfx950 code objects, parsed from the
+    mangled names (screen_kernel, screen_ar_kernelILi<KBN>ELi<DIAG>ELb<I8>EE, ...)."""
+    import subprocess
+
+    found = set()
+    for j, co in enumerate(_gfx950_code_objects(lib_path)):
+        f = tmp_path / f"scco{j}.o"
+        f.write_bytes(co)
+        notes = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True).stdout
+        for ln in notes.splitlines():
+            ln = ln.strip()
+            if not ln.startswith(".name:") or "10ScreenArgs" not in ln:
+                continue
+            m = re.search(r"\d+(screen\w*_kernel)(?:I((?:L[ib]\d+E)+)E)?", ln)
+            assert m, ln
+            found.add((m.group(1), tuple(int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2) or ""))))
+    return found
+
+
+def test_product_screen_kernels_are_the_pinned_set(tmp_path):
+    """The product library holds exactly the eight screen kernels launch_screen's table
+    names: K3c, K3d <KBN, DIAG, I8> for 16 / 24 bf16 and 8 / 12 / 16 int8 K blocks, K3i
+    2 x 2 <KBN, DIAG> for 8 / 12 -- no diagnostic (DIAG != 0) and no retired variant.
+    A new instantiation fails here until tests/test_gpu_screen.py covers it."""
+    from weaviate_amd import _lib
+
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not os.path.exists(readelf):
+        pytest.skip("llvm-readelf not available")
+    found = _screen_instantiations(_lib.LIB_PATH, tmp_path, readelf)
+    assert found == {
+        ("screen_kernel", ()),
+        ("screen_ar_kernel", (16, 0, 0)), ("screen_ar_kernel", (24, 0, 0)),
+        ("screen_ar_kernel", (8, 0, 1)), ("screen_ar_kernel", (12, 0, 1)), ("screen_ar_kernel", (16, 0, 1)),
+        ("screen_i8_kernel", (8, 0)), ("screen_i8_kernel", (12, 0)),
+    }, sorted(found)

@@ -255,7 +255,6 @@ int wvg_open_ex(int device, const wvg_options *opts, wvg_ctx **out)
     if (const char *e = getenv("WVG_SERPENTINE")) tuning().serpentine = (int)strtol(e, nullptr, 10);  // A/B runs
     if (const char *e = getenv("WVG_K1_TAIL")) tuning().k1_tail = (int)strtol(e, nullptr, 10);        // A/B runs
     if (const char *e = getenv("WVG_K1_LOADS")) tuning().k1_loads = (int)strtol(e, nullptr, 10);        // A/B runs
-    if (const char *e = getenv("WVG_SCREEN_VARIANT")) tuning().screen_variant = (int)strtol(e, nullptr, 10);  // A/B
     if (const char *e = getenv("WVG_STREAM_VARIANT")) tuning().stream_variant = (int)strtol(e, nullptr, 10);  // A/B
     if (const char *e = getenv("WVG_SCREEN_SP")) tuning().screen_pilot_screen = (int)strtol(e, nullptr, 10);  // A/B
     if (const char *e = getenv("WVG_GROUPS_PER_CU")) tuning().groups_per_cu = (int)strtol(e, nullptr, 10);  // A/B

@@ -577,9 +577,10 @@ struct Tuning {
     int screen_round = 1;    // screen row ranges (tuning key 33): 1 = nrr * query blocks a multiple of the CUs
     int screen_pilot_gemm_i8 = 256;  // the same for K3i (tuning key 32): with its warm-up ranges half the
                                      // pilot is ~1 % faster per batch (profiles/r06/screen_i8/pilot_tiles_ab*.jsonl)
-    int screen_variant = 0;  // batched screen kernel: 0 = K3d where it applies (d = 512, 768), 1 = K3c,
-                             // 2 = K3e (K3d with 32x32x16 MFMAs), 3 = K3f (two waves per SIMD); 2 and 3
-                             // exist in the tools build only (profiles/r05/k3e, k3f)
+    int screen_variant = 0;  // batched screen kernel (tuning key 20): 0 = the default (K3i 2 x 2 / K3d where they
+                             // apply, else K3c), 1 = K3c everywhere (bf16 shadow), 5 = K3i on K3d's 1 x 4 wave
+                             // layout (int8 shadow); any other value, or one the shadow's kind does not
+                             // have, fails the launch
     int stream_variant = 1;  // query-stream K1 (tuning key 25): bit 0 = tile-granular wave ranges (the default:
                              // row-granular ranges let every wave touch one more, shared tile, and a wave's time
                              // follows its tile count -- 85.1 vs 82.5 us per 1M-row query, profiles/r05/stream_ab/),
@@ -627,8 +628,10 @@ struct Tuning {
                              // folded (A/B; profiles/r12/qshare_screen/)
     int multi_bq_bound = 1;  // multi-GPU BQ heap flow (tuning key 36): 1 = the cross-slab bound X_s in the filter,
                              // 0 = every slab filters with its own thresholds only (A/B: rows replayed)
-    int screen_diag = 0;     // K3c diagnostics (tools build only; results are NOT distances): bit 0 = no
-                             // wait for the stage loads, bit 1 = no epilogue, bit 2 = no list insertions, bit 3 = no query-fragment loads (K3c); K3d: 1, 2, 4 or 16 (= counters) select compiled variants
+    int screen_diag = 0;     // K3d / K3i diagnostics (tuning key 18, tools build only): 4 = the fast check but no
+                             // exact path, 10 = the stage loop and MFMAs alone (4, 10: results are NOT
+                             // distances), 16 = counters (screen_counters); a value with no compiled kernel
+                             // for the launch's (int8, K blocks) fails the launch
 };
 #ifdef WVG_TOOLS
 Tuning &tuning();

@@ -1,7 +1,17 @@
-// wvg_screen.hip -- K3c: batched dot / cosine scoring as a bf16 MFMA screen
-// with a rigorous per-(query, row) error bound, followed by the exact fp32
-// rescore of every row the bound cannot rule out.  Results are bit-identical
-// to the exact path (K3b / K1, the reference's AVX2-order dot_256):
+// wvg_screen.hip -- the batched screen: dot / cosine scoring on the matrix
+// pipe with a rigorous per-(query, row) error bound, followed by the exact
+// fp32 rescore of every row the bound cannot rule out.  Three kernels, one
+// bound, one list / partials format (launch_screen's table picks one):
+//   K3c  screen_kernel: bf16, queries and rows both staged through LDS; any
+//        d % 32 == 0 (below, "K3c").
+//   K3d  screen_ar_kernel<KBN, 0, false>: bf16, the queries resident in
+//        registers, 1 x 4 waves; d = 512, 768 ("K3d").
+//   K3i  the int8 shadow at twice the MFMA rate ("The int8 screen"):
+//        screen_i8_kernel<KBN, 0>, 2 x 2 waves, d = 512 / 768 (the default
+//        there), and screen_ar_kernel<KBN, 0, true>, K3d's layout, d = 1024.
+// A non-zero DIAG instantiates a timing / counting diagnostic of K3d or K3i
+// (tools build only).  Results are bit-identical to the exact path (K3b / K1,
+// the reference's AVX2-order dot_256):
 //
 //   Reference: Q independent flat.searchByVector calls (V/flat/index.go:319)
 //   over the same rows, SingleDist = dot_256 (D/dot_product.go:68-98,
@@ -446,9 +456,6 @@ struct ScreenArgs {
     uint64_t bsplit[2];       // [rsplit[0], rsplit[1]) blocks [bsplit[0], bsplit[1]) (short warm-up
                               // ranges), the others the rest; rsplit[0] = 0: nrr equal ranges
     int cosine;
-#ifdef WVG_TOOLS
-    int diag;                 // Tuning::screen_diag
-#endif
     uint32_t *gbound;         // [nq] ordered tau; 0xFFFFFFFF = none yet
     uint64_t *partials;       // [nq][nrr][SCREEN_M]
 };
@@ -544,6 +551,90 @@ __device__ __attribute__((noinline)) float sc_insert(lds_u64 *L, lds_f32 *WT, ld
     return ws;
 }
 
+// ---------------------------------------------------------------------------
+// The prologue and tile-word handling that K3c, K3d and K3i share.
+
+// Workgroup -> (query block, row range): the nqb query blocks of one row range
+// share an XCD (blocks b, b + 8, ...)
+__device__ __forceinline__ void sc_block_map(const ScreenArgs &a, uint32_t &qb, uint32_t &rr)
+{
+    const uint32_t b = blockIdx.x;
+    if (a.nrr_l % 8 == 0) {
+        const uint32_t xcd = b % 8, wv = b / 8;
+        qb = wv % a.nqb;
+        rr = a.rr0 + (wv / a.nqb) * 8 + xcd;
+    } else {
+        qb = b % a.nqb;
+        rr = a.rr0 + b / a.nqb;
+    }
+}
+
+// The workgroup's 128 queries' constants into LDS (I8: also B and the score scale)
+template <bool I8>
+__device__ __forceinline__ void sc_copy_consts(const ScreenArgs &a, uint32_t q0, int nthreads, float *ck1, float *ck2,
+                                               float *cem, float *ckb, float *ccs)
+{
+    for (int i = threadIdx.x; i < SC_BQ; i += nthreads) {
+        const uint32_t q = q0 + (uint32_t)i;
+        ck1[i] = a.k1[q];
+        ck2[i] = a.k2[q];
+        cem[i] = a.emax[q];
+        if constexpr (I8) {
+            ckb[i] = a.kb[q];
+            ccs[i] = a.css[q];
+        }
+    }
+}
+
+// The WAVES x QW (wave, query) threshold slots from gbound: tau (distance
+// space) and sig (u space).  A wave holds QW queries and the workgroup's
+// queries are split over NQW waves (the others take other rows), so slot
+// (w, ql) is query QW (w % NQW) + ql of the block.  A query past nq admits
+// nothing.  (Compile-time geometry, not a functor argument: with a lambda for
+// the map K3d's schedule and register allocation came out different.)
+template <int QW, int NQW, int WAVES>
+__device__ __forceinline__ void sc_init_thresholds(const ScreenArgs &a, uint32_t q0, int tid, int cosine, float *tau,
+                                                   float *sig)
+{
+    for (int i = tid; i < WAVES * QW; i += WAVES * 64) {
+        const uint32_t q = q0 + (uint32_t)(((i / QW) % NQW) * QW + i % QW);
+        // agent-scope load (L1 bypassed): the bounds are atomicMin'd by ranges that
+        // finished on any XCD; a plain load could return a stale line
+        const uint32_t g = q < a.nq ? __hip_atomic_load(a.gbound + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        const float t = q >= a.nq ? -__builtin_inff() : (g == 0xFFFFFFFFu ? __builtin_inff() : wvg_unord_f32(g));
+        tau[i] = t;
+        sig[i] = q >= a.nq ? __builtin_inff() : sc_sigma(t, cosine);
+    }
+}
+
+// Row block blk's tile words as dwords, one per lane of the loading wave:
+// lanes 0-7 validity (tile lane >> 1, half lane & 1), 8-15 allow; addresses
+// clamped into the arrays (the mask assembly drops what lies outside).  The
+// epilogue reads them from LDS (a scalar load there waited the full memory
+// latency: the words fall out of L2 behind the row stream).
+__device__ __forceinline__ const uint32_t *sc_tile_word_src(const ScreenArgs &a, uint64_t blk, int lane)
+{
+    const uint32_t wi = (uint32_t)(lane & 7) >> 1, half = lane & 1;
+    const uint64_t t = a.tile_begin + blk * 4 + wi;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(a.valid + (t < a.tile_end ? t : a.tile_end - 1)) + half;
+    if (lane >= 8 && lane < 16 && a.allow) {
+        const uint64_t aw = t - a.allow_t0;
+        src = reinterpret_cast<const uint32_t *>(a.allow + (aw < a.allow_words ? aw : 0)) + half;
+    }
+    return src;
+}
+
+// Tile t's live-row mask (valid & allow) from its staged words (a lane's copy each)
+__device__ __forceinline__ uint64_t sc_tile_mask(const ScreenArgs &a, uint64_t t, uint64_t word, uint64_t allow)
+{
+    uint64_t m = t < a.tile_end ? readfirstlane64(word) : 0ull;
+    if (a.allow) {
+        const uint64_t aw = t - a.allow_t0;
+        m &= aw < a.allow_words ? readfirstlane64(allow) : 0ull;
+    }
+    return m;
+}
+
 #ifdef WVG_TOOLS
 __device__ unsigned long long g_screen_ctr[4];  // tools build: [0] row blocks, [1] slow-path entries, [2] insert calls
 #endif
@@ -566,17 +657,8 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
     const int wq = w & 3, wr = w >> 2;
     const int K = (int)a.k, M = SCREEN_M;
     const int cosine = a.cosine;
-    // the nqb query blocks of one row range share an XCD (blocks b, b+8, ...)
-    const uint32_t b = blockIdx.x;
     uint32_t qb, rr;
-    if (a.nrr_l % 8 == 0) {
-        const uint32_t xcd = b % 8, wv = b / 8;
-        qb = wv % a.nqb;
-        rr = a.rr0 + (wv / a.nqb) * 8 + xcd;
-    } else {
-        qb = b % a.nqb;
-        rr = a.rr0 + b / a.nqb;
-    }
+    sc_block_map(a, qb, rr);
     const uint64_t ntiles = a.tile_end - a.tile_begin;
     const uint64_t nblk = (ntiles + 3) / 4;  // 256-row blocks
     const uint64_t blk0 = nblk * rr / a.nrr, blk1 = nblk * (rr + 1) / a.nrr;
@@ -584,22 +666,8 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
     const uint32_t NK = a.kbn;  // 32-deep stages per row block
 
     // per-query constants and thresholds
-    for (int i = tid; i < SC_BQ; i += SC_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        ck1[i] = a.k1[q];
-        ck2[i] = a.k2[q];
-        cem[i] = a.emax[q];
-    }
-    for (int i = tid; i < SC_WAVES * 32; i += SC_WAVES * 64) {
-        const int ww = i / 32, ql = i % 32;
-        const uint32_t q = q0 + (uint32_t)((ww & 3) * 32 + ql);
-        // agent-scope load (L1 bypassed): the bounds are atomicMin'd by ranges that
-        // finished on any XCD; a plain load could return a stale line
-        const uint32_t g = q < a.nq ? __hip_atomic_load(a.gbound + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const float t = q >= a.nq ? -__builtin_inff() : (g == 0xFFFFFFFFu ? __builtin_inff() : wvg_unord_f32(g));
-        tau[i] = t;
-        sig[i] = q >= a.nq ? __builtin_inff() : sc_sigma(t, cosine);
-    }
+    sc_copy_consts<false>(a, q0, SC_WAVES * 64, ck1, ck2, cem, nullptr, nullptr);
+    sc_init_thresholds<32, 4, SC_WAVES>(a, q0, tid, cosine, tau, sig);  // 4 query quarters x 2 row halves
     for (int i = tid; i < SC_WAVES * 32 * M; i += SC_WAVES * 64) lists[i] = WVG_KEY_NONE;
     __syncthreads();
     if (blk0 >= blk1) goto publish;
@@ -634,9 +702,6 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
         auto load_stage = [&](unsigned char *dst, uint32_t ks, uint64_t lb) {
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-#ifdef WVG_TOOLS
-                if ((a.diag & 8) && 3 * w + j < SC_AFR) continue;  // diagnostic: no query-fragment loads
-#endif
                 __builtin_amdgcn_global_load_lds(lsrc[j] + (size_t)ks * lstep[j],
                                                  reinterpret_cast<uint4 *>(dst + (3 * w + j) * 1024), 16, 0, 0);
             }
@@ -644,19 +709,8 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
                 __builtin_amdgcn_global_load_lds(lnorm, reinterpret_cast<float *>(dst + (SC_AFR + SC_BFR) * 1024 + w * 256),
                                                  4, 0, 0);
             if (w == 4) {
-                // the block's tile words as dwords: lanes 0-7 validity (tile
-                // lane >> 1, half lane & 1), 8-15 allow; the epilogue reads them
-                // from LDS (a scalar load there waited the full memory latency:
-                // the words fall out of L2 behind the row stream)
-                const uint32_t wi = (uint32_t)(lane & 7) >> 1, half = lane & 1;
-                const uint64_t t = a.tile_begin + lb * 4 + wi;
-                const uint32_t *src = reinterpret_cast<const uint32_t *>(a.valid + (t < a.tile_end ? t : a.tile_end - 1)) + half;
-                if (lane >= 8 && lane < 16 && a.allow) {
-                    const uint64_t aw = t - a.allow_t0;
-                    src = reinterpret_cast<const uint32_t *>(a.allow + (aw < a.allow_words ? aw : 0)) + half;
-                }
-                __builtin_amdgcn_global_load_lds(src, reinterpret_cast<uint32_t *>(dst + (SC_AFR + SC_BFR + 1) * 1024),
-                                                 4, 0, 0);
+                __builtin_amdgcn_global_load_lds(sc_tile_word_src(a, lb, lane),
+                                                 reinterpret_cast<uint32_t *>(dst + (SC_AFR + SC_BFR + 1) * 1024), 4, 0, 0);
             }
         };
         auto next_block = [&]() {  // the load cursor moves to the next row block
@@ -666,9 +720,6 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
         };
         // wait until at most `younger` stages' loads of this wave are in flight
         auto wait_stages = [&](int younger) {
-#ifdef WVG_TOOLS
-            if (a.diag & 1) return;
-#endif
             if (w < 5) {
                 if (younger >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
                 else if (younger == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -740,12 +791,7 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
                     for (int nr = 0; nr < 8; nr++)
                         acc[mq][nr] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[mq], bv[nr], acc[mq][nr], 0, 0, 0);
             }
-#ifdef WVG_TOOLS
-            const bool epi = ks == NK - 1 && !(a.diag & 2);
-#else
-            const bool epi = ks == NK - 1;
-#endif
-            if (epi) {
+            if (ks == NK - 1) {
                 // epilogue of row block blk: C layout row (query) qlane + r, column (row) lane & 15
                 // The epilogue's LDS reads go through inline asm: the compiler's
                 // wait pass cannot tell them from reads of an in-flight LDS DMA
@@ -782,13 +828,7 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
                     const uint64_t allows[2] = {((uint64_t)aw4.y << 32) | aw4.x, ((uint64_t)aw4.w << 32) | aw4.z};
 #pragma unroll
                     for (int h = 0; h < 2; h++) {
-                        const uint64_t t = a.tile_begin + blk * 4 + 2 * wr + h;
-                        uint64_t m = t < a.tile_end ? readfirstlane64(words[h]) : 0ull;
-                        if (a.allow) {
-                            const uint64_t aw = t - a.allow_t0;
-                            m &= aw < a.allow_words ? readfirstlane64(allows[h]) : 0ull;
-                        }
-                        vm[h] = m;
+                        vm[h] = sc_tile_mask(a, a.tile_begin + blk * 4 + 2 * wr + h, words[h], allows[h]);
                     }
                 }
                 float k1r[2][4], k2r[2][4], svr[2][4];
@@ -835,12 +875,10 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
                     mnr_a[nr] = mnr;
                     mx = __builtin_fmaxf(mx, mnr);
                 }
+                const bool slow = __ballot(mx >= 0.f);
 #ifdef WVG_TOOLS
                 n_blk++;
-                const bool slow = __ballot(mx >= 0.f) && !(a.diag & 4);
                 n_slow += slow;
-#else
-                const bool slow = __ballot(mx >= 0.f);
 #endif
                 if (slow) {
                 // only the row groups where some lane passed the fast check (their
@@ -1026,32 +1064,28 @@ __device__ __forceinline__ void sd_static_for(F &&f)
 
 // Vector-memory loads one K3d wave issues for unit u (K block u of a row
 // block): its 4 row-fragment pieces, and with unit 0 the block's row norms of
-// its tile (+ wave 0: the block's tile words).  DIAG 256 (tools): round 3's
-// norms / words with every unit.
-template <int DIAG, bool I8 = false>
+// its tile (+ wave 0: the block's tile words).
+template <bool I8 = false>
 constexpr int sd_unit_loads(int u, bool w0)
 {
-    if ((DIAG & 128) != 0) return 0;
-    if ((DIAG & 32) != 0) return 4;
-    if ((DIAG & 256) != 0) return 5 + (w0 ? 1 : 0);
     return 4 + (u == 0 ? 1 + (I8 ? 1 : 0) + (w0 ? 1 : 0) : 0);  // (K3i: + the row errors)
 }
 // The loads issued after unit `first`'s, over units first + 1 .. first + n (mod KBN)
-template <int KBN, int DIAG, bool I8 = false>
+template <int KBN, bool I8 = false>
 constexpr int sd_younger(int first, int n, bool w0)
 {
     int c = 0;
-    for (int i = 1; i <= n; i++) c += sd_unit_loads<DIAG, I8>((first + i) % KBN, w0);
+    for (int i = 1; i <= n; i++) c += sd_unit_loads<I8>((first + i) % KBN, w0);
     return c;
 }
 
-// DIAG (tools build only; 0 in the product): bit 0 = no wait for the stage
-// loads, bit 1 = no epilogue (alone it lets the compiler delete the MFMAs, as
-// the round-3 "stage loop alone" diagnostics did: their 8.3 ms had no MFMA),
-// bit 1 + bit 3 (10) = the stage loop with its MFMAs and a one-sum consumer,
-// bit 2 = tests but no survivor queue, bit 4 = count row blocks / blocks with
-// survivors / queued survivors.  Compile-time, so the tools build's DIAG = 0
-// kernel is the product kernel, register allocation included.
+// DIAG (tools build only; 0 in the product): 4 = the fast check but no exact
+// path, 10 = the stage loop alone with its MFMAs and a one-sum consumer (with
+// no consumer the compiler deletes the MFMAs), 16 = count row blocks / blocks
+// with survivors / inserted survivors / active groups.  4 and 10 time the
+// kernel only: their results are not search results.  Compile-time, so the
+// tools build's DIAG = 0 kernel is the product kernel, register allocation
+// included.
 //
 // I8 (K3i, round 6): the same kernel on the int8 shadow -- 64-deep K blocks
 // of v_mfma_i32_16x16x64_i8 (twice the bf16 rate: a K block is the same
@@ -1065,7 +1099,8 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
     constexpr int NSLOT = I8 ? SI_NSLOT : SD_NSLOT;
     constexpr int RING = NB * SD_STAGE + 2 * NSLOT;
     static_assert(KBN % NB == 0, "the stage buffer of a K block must be a compile-time constant");
-    static_assert(!I8 || (DIAG & ~(2 | 8)) == 0, "K3i: only the stage-loop diagnostic");
+    static_assert(DIAG == 0 || DIAG == 10 || (!I8 && (DIAG == 4 || DIAG == 16)),
+                  "diagnostics: 4, 10, 16 (K3i: only the stage-loop one)");
     using frag_t = std::conditional_t<I8, i32x4, bf16x8>;
     using acc_t = std::conditional_t<I8, i32x4, floatx4>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1077,45 +1112,22 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
     float *cem = ck2 + SD_BQ;
     float *ckb = cem + SD_BQ;  // (I8) B
     float *ccs = ckb + SD_BQ;  // (I8) score scale
-    uint32_t n_blk = 0, n_slow = 0, n_call = 0, n_grp = 0;  // (DIAG & 16)
+    uint32_t n_blk = 0, n_slow = 0, n_call = 0, n_grp = 0;  // (DIAG 16)
     (void)n_blk, (void)n_slow, (void)n_call, (void)n_grp;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int K = (int)a.k, M = SCREEN_M;
     const int cosine = a.cosine;
-    const uint32_t b = blockIdx.x;
     uint32_t qb, rr;
-    if (a.nrr_l % 8 == 0) {
-        const uint32_t xcd = b % 8, wv = b / 8;
-        qb = wv % a.nqb;
-        rr = a.rr0 + (wv / a.nqb) * 8 + xcd;
-    } else {
-        qb = b % a.nqb;
-        rr = a.rr0 + b / a.nqb;
-    }
+    sc_block_map(a, qb, rr);
     const uint64_t ntiles = a.tile_end - a.tile_begin;
     const uint64_t nblk = (ntiles + 3) / 4;
     uint64_t blk0, blk1;
     sc_range(a, nblk, rr, blk0, blk1);
     const uint32_t q0 = qb * SD_BQ;
 
-    for (int i = tid; i < SD_BQ; i += SD_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        ck1[i] = a.k1[q];
-        ck2[i] = a.k2[q];
-        cem[i] = a.emax[q];
-        if constexpr (I8) {
-            ckb[i] = a.kb[q];
-            ccs[i] = a.css[q];
-        }
-    }
-    for (int i = tid; i < SD_WAVES * 32; i += SD_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        const uint32_t g = q < a.nq ? __hip_atomic_load(a.gbound + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const float t = q >= a.nq ? -__builtin_inff() : (g == 0xFFFFFFFFu ? __builtin_inff() : wvg_unord_f32(g));
-        tau[i] = t;
-        sig[i] = q >= a.nq ? __builtin_inff() : sc_sigma(t, cosine);
-    }
+    sc_copy_consts<I8>(a, q0, SD_WAVES * 64, ck1, ck2, cem, ckb, ccs);
+    sc_init_thresholds<32, 4, SD_WAVES>(a, q0, tid, cosine, tau, sig);  // 4 query quarters, every row
     for (int i = tid; i < SD_WAVES * 32 * M; i += SD_WAVES * 64) lists[i] = WVG_KEY_NONE;
     __syncthreads();
     SurvivorLists S;
@@ -1164,7 +1176,6 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
         const float *lerr = I8 ? a.errs + (a.tile_begin + blk0 * 4 + w) * 64 + lane : nullptr;
         uint64_t lblk = blk0;
         auto load_stage = [&](int ks) {
-            if constexpr ((DIAG & 128) != 0) return;
             unsigned char *dst = smem + (ks % NB) * SD_STAGE;
 #pragma unroll
             for (int rg = 0; rg < 4; rg++)
@@ -1172,21 +1183,14 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                                                  reinterpret_cast<uint4 *>(dst + (4 * w + rg) * 1024), 16, 0, 0);
             unsigned char *nslot = smem + NB * SD_STAGE + (lblk & 1) * NSLOT;
             // the block's norms / tile words with its unit 0 (sd_unit_loads: the waits count them)
-            const bool with_norms = (DIAG & 32) == 0 && ((DIAG & 256) != 0 || ks == 0);
+            const bool with_norms = ks == 0;
             if (with_norms)
                 __builtin_amdgcn_global_load_lds(lnorm, reinterpret_cast<float *>(nslot + w * 256), 4, 0, 0);
             if (I8 && with_norms)
                 __builtin_amdgcn_global_load_lds(lerr, reinterpret_cast<float *>(nslot + 1280 + w * 256), 4, 0, 0);
             if (with_norms && w == 0) {
-                const uint32_t wi = (uint32_t)(lane & 7) >> 1, half = lane & 1;
-                const uint64_t t = a.tile_begin + lblk * 4 + wi;
-                const uint32_t *src =
-                    reinterpret_cast<const uint32_t *>(a.valid + (t < a.tile_end ? t : a.tile_end - 1)) + half;
-                if (lane >= 8 && lane < 16 && a.allow) {
-                    const uint64_t aw = t - a.allow_t0;
-                    src = reinterpret_cast<const uint32_t *>(a.allow + (aw < a.allow_words ? aw : 0)) + half;
-                }
-                __builtin_amdgcn_global_load_lds(src, reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds(sc_tile_word_src(a, lblk, lane),
+                                                 reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
             }
             if (ks == KBN - 1 && lblk + 1 < blk1) {  // the load cursor moves on; past the end it stays
                 ++lblk;
@@ -1197,24 +1201,17 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
         };
         // six stages in flight at every wait: unit ks + 1 (waited for at K block ks) + the 5
         // younger units ks + 2 .. ks + 6, whose loads the wait leaves outstanding
-        // PAIR (tools A/B, DIAG 1024): one wait + barrier per two K blocks -- at even ks for
-        // unit ks + 2 (units ks + 3 .. ks + 6 outstanding), which also covers the odd
-        // iteration's reads of unit ks + 1; the two units ks + 7, ks + 8 load after it
         // (K3i with NB = 6: four stages in flight, three left outstanding)
-        constexpr bool PAIR = (DIAG & 1024) != 0;
         auto wait_next = [&](auto KS) {
-            if constexpr ((DIAG & 129) != 0) return;
             constexpr int ks = decltype(KS)::value;
-            if constexpr (PAIR && (ks & 1) != 0) return;
-            constexpr int first = PAIR ? ks + 2 : ks + 1, n = PAIR ? NB - 4 : NB - 3;
-            constexpr int n0 = sd_younger<KBN, DIAG, I8>(first, n, true);
-            constexpr int n1 = sd_younger<KBN, DIAG, I8>(first, n, false);
+            constexpr int n0 = sd_younger<KBN, I8>(ks + 1, NB - 3, true);
+            constexpr int n1 = sd_younger<KBN, I8>(ks + 1, NB - 3, false);
             if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n0) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n1) : "memory");
         };
         auto raw_barrier = [&]() {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if constexpr ((DIAG & 64) == 0) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         };
         // Half a stage's row fragments straight into AGPRs (the MFMA B operand may
@@ -1285,8 +1282,8 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
 #pragma unroll
         for (int ks = 0; ks < NB - 1; ks++) load_stage(ks);
         // unit 0 landed: the NB - 2 younger units outstanding
-        if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, DIAG, I8>(0, NB - 2, true)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, DIAG, I8>(0, NB - 2, false)) : "memory");
+        if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, I8>(0, NB - 2, true)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, I8>(0, NB - 2, false)) : "memory");
         raw_barrier();
         read_half(0, 0, b0);
         for (uint64_t blk = blk0; blk < blk1; blk++) {
@@ -1299,20 +1296,11 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
 #pragma unroll
                     for (int nr = 0; nr < 8; nr++) acc[mq][nr] = mfma(areg[ks][mq], b0[nr], acc[mq][nr]);
                 wait_next(KS);  // the next unit landed
-                if constexpr (!PAIR || (ks & 1) == 0)
-                    raw_barrier();  // (lgkmcnt(0): this wave's second-half reads done)
-                else
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                raw_barrier();  // (lgkmcnt(0): this wave's second-half reads done)
 #pragma unroll
                 for (int j = 0; j < 8; j++) asm volatile("" : "+a"(b1[j]));
-                // unit + 7 into the buffer of unit - 1 (fully read before this barrier); PAIR:
-                // also unit + 8 into the buffer of this unit (its reads done: the barrier's wait)
-                if constexpr (!PAIR) {
-                    load_stage((ks + NB - 1) % KBN);
-                } else if constexpr ((ks & 1) == 0) {
-                    load_stage((ks + NB - 1) % KBN);
-                    load_stage((ks + NB) % KBN);
-                }
+                // unit + 7 into the buffer of unit - 1 (fully read before this barrier)
+                load_stage((ks + NB - 1) % KBN);
                 if (ks + 1 < KBN) read_half(ks + 1, 0, b0);  // (the next block's first half: after the epilogue)
 #pragma unroll
                 for (int mq = 0; mq < 2; mq++)
@@ -1329,7 +1317,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
             __builtin_amdgcn_sched_barrier(0);
             // epilogue of row block blk (K3c's, over 16 row groups): C layout row
             // (query) qlane + r, column (row) 16 nr + (lane & 15)
-            if constexpr ((DIAG & 2) == 0) {
+            if constexpr (DIAG != 10) {
                 // Fast check per query group, then the exact test !(u < WS) (NaN-safe: a
                 // non-finite row or query always passes) on the groups the check could not
                 // rule out, survivors inserted into register-held lists (the slow path
@@ -1390,17 +1378,13 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                     csr[0] = csv.x, csr[1] = csv.y, csr[2] = csv.z, csr[3] = csv.w;
                 };
                 (void)read_consts_i8;
-                if constexpr ((DIAG & 16) != 0) n_blk++;
+                if constexpr (DIAG == 16) n_blk++;
                 // fast check: the lane's 16 rows' largest norm bound bounds each of their E
                 // (E = fma(norm, K1q, K2q) is monotone in the norm), so per query the largest
                 // raw score of the lane's rows + that E against WS is a superset test of
                 // every element (monotone roundings); finite on the fast-eligible inputs
                 // (query K1 <= 2^50, row norms <= 2^60), else the exact test runs
-                // TIGHT (tools A/B, DIAG 2048): the check on each element's own u (its row's E),
-                // i.e. exactly the exact test's verdict per group, at 32 more VALU per group
-                constexpr bool TIGHT = (DIAG & 2048) != 0;
                 float nmax, nsum;  // (nsum: NaN when a norm is -- fmaxf would drop it)
-                float nrmt[TIGHT ? 16 : 1];
                 {
                     float n0[8], n1[8];
                     read_norms8(0, n0);
@@ -1411,10 +1395,6 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                     for (int j2 = 1; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n0[j2]), nsum += n0[j2];
 #pragma unroll
                     for (int j2 = 0; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n1[j2]), nsum += n1[j2];
-                    if constexpr (TIGHT) {
-#pragma unroll
-                        for (int j2 = 0; j2 < 8; j2++) nrmt[j2] = n0[j2], nrmt[8 + j2] = n1[j2];
-                    }
                 }
                 // (I8) the lane's 16 rows' largest error bound: E = fma(err, A, fma(norm, B, K2))
                 // is monotone in both
@@ -1457,23 +1437,14 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                     }
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
-                        float t;
-                        if constexpr (TIGHT) {
-                            float m = -__builtin_inff();
+                        float m = agpr_read(acc[mq][0][r]);
 #pragma unroll
-                            for (int nr = 0; nr < 16; nr++)
-                                m = __builtin_fmaxf(m, agpr_read(acc[mq][nr][r]) + __builtin_fmaf(nrmt[nr], k1r[r], k2r[r]));
-                            t = m - svr[r];
-                        } else {
-                            float m = agpr_read(acc[mq][0][r]);
-#pragma unroll
-                            for (int nr = 1; nr < 16; nr++) m = __builtin_fmaxf(m, agpr_read(acc[mq][nr][r]));
-                            t = (m + __builtin_fmaf(nmax, k1r[r], k2r[r])) - svr[r];
-                        }
+                        for (int nr = 1; nr < 16; nr++) m = __builtin_fmaxf(m, agpr_read(acc[mq][nr][r]));
+                        const float t = (m + __builtin_fmaf(nmax, k1r[r], k2r[r])) - svr[r];
                         if (__ballot(force || t >= 0.f)) wact |= 1u << (4 * mq + r);
                     }
                 }
-                const bool slow = wact != 0 && (DIAG & 4) == 0;
+                const bool slow = wact != 0 && DIAG != 4;
                 if (slow) {
                     uint64_t vm[4];
                     {
@@ -1494,17 +1465,11 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                                                     ((uint64_t)aw1.y << 32) | aw1.x, ((uint64_t)aw1.w << 32) | aw1.z};
 #pragma unroll
                         for (int h = 0; h < 4; h++) {
-                            const uint64_t t = a.tile_begin + blk * 4 + h;
-                            uint64_t m = t < a.tile_end ? readfirstlane64(words[h]) : 0ull;
-                            if (a.allow) {
-                                const uint64_t aw = t - a.allow_t0;
-                                m &= aw < a.allow_words ? readfirstlane64(allows[h]) : 0ull;
-                            }
-                            vm[h] = m;
+                            vm[h] = sc_tile_mask(a, a.tile_begin + blk * 4 + h, words[h], allows[h]);
                         }
                     }
                     const uint64_t slot0 = (a.tile_begin + blk * 4) * 64;
-                    if constexpr ((DIAG & 16) != 0) n_slow++;
+                    if constexpr (DIAG == 16) n_slow++;
                     // Per active group gi = (mq, r): lane l tests its column's 16 rows against
                     // query ql = 16 mq + r + qlane (C layout), and row l >> 4 of the register v
                     // holds that same query's list (lane l: entry l & 15) -- the four queries of
@@ -1523,7 +1488,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                     }
                     for (uint32_t gw = wact; gw; gw &= gw - 1) {
                         const int gi = __builtin_ctz(gw);
-                        if constexpr ((DIAG & 16) != 0) n_grp++;
+                        if constexpr (DIAG == 16) n_grp++;
                         float uv[16];  // (I8: the exact int32 scores, exactly as floats: |score| < 2^24)
                         switch (gi) {
 #define WVG_SD_GROUP(G)                                                                        \
@@ -1577,7 +1542,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                                     sc_lower(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j)), cosine);
                                 float wtg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wt), j));
                                 if (!(lower <= wtg)) continue;
-                                if constexpr ((DIAG & 16) != 0) n_call++;
+                                if constexpr (DIAG == 16) n_call++;
                                 const uint64_t key = ((uint64_t)wvg_ord_f32(lower) << 32) |
                                                      (uint32_t)(slot0 + 16u * (uint32_t)nr + (uint32_t)(j & 15));
                                 if (!(key < readlane64(v, 16 * g + SCREEN_M - 1))) continue;
@@ -1606,7 +1571,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
                     }
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 }
-            } else if constexpr ((DIAG & 8) != 0) {
+            } else {
                 // diagnostic (DIAG 10): the stage loop alone -- the accumulators are consumed by
                 // one sum, so the MFMAs stay (without any consumer the compiler removes them)
                 float x = 0.f;
@@ -1627,7 +1592,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_kernel(ScreenArgs 
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef WVG_TOOLS
-    if constexpr ((DIAG & 16) != 0) {
+    if constexpr (DIAG == 16) {
         if (lane == 0) {
             atomicAdd(&g_screen_ctr[0], (unsigned long long)n_blk);
             atomicAdd(&g_screen_ctr[1], (unsigned long long)n_slow);
@@ -1694,37 +1659,16 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
     const int wq = w & 1, wr = w >> 1;  // query half (64 queries), row half (tiles 2 wr, 2 wr + 1)
     const int K = (int)a.k, M = SCREEN_M;
     const int cosine = a.cosine;
-    const uint32_t b = blockIdx.x;
     uint32_t qb, rr;
-    if (a.nrr_l % 8 == 0) {
-        const uint32_t xcd = b % 8, wv = b / 8;
-        qb = wv % a.nqb;
-        rr = a.rr0 + (wv / a.nqb) * 8 + xcd;
-    } else {
-        qb = b % a.nqb;
-        rr = a.rr0 + b / a.nqb;
-    }
+    sc_block_map(a, qb, rr);
     const uint64_t ntiles = a.tile_end - a.tile_begin;
     const uint64_t nblk = (ntiles + 3) / 4;
     uint64_t blk0, blk1;
     sc_range(a, nblk, rr, blk0, blk1);
     const uint32_t q0 = qb * SD_BQ;
 
-    for (int i = tid; i < SD_BQ; i += SD_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        ck1[i] = a.k1[q];
-        ck2[i] = a.k2[q];
-        cem[i] = a.emax[q];
-        ckb[i] = a.kb[q];
-        ccs[i] = a.css[q];
-    }
-    for (int i = tid; i < SD_WAVES * 64; i += SD_WAVES * 64) {  // (wave v, query ql) = (i / 64, i % 64)
-        const uint32_t q = q0 + (uint32_t)(64 * ((i >> 6) & 1) + (i & 63));
-        const uint32_t g = q < a.nq ? __hip_atomic_load(a.gbound + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const float t = q >= a.nq ? -__builtin_inff() : (g == 0xFFFFFFFFu ? __builtin_inff() : wvg_unord_f32(g));
-        tau[i] = t;
-        sig[i] = q >= a.nq ? __builtin_inff() : sc_sigma(t, cosine);
-    }
+    sc_copy_consts<true>(a, q0, SD_WAVES * 64, ck1, ck2, cem, ckb, ccs);
+    sc_init_thresholds<64, 2, SD_WAVES>(a, q0, tid, cosine, tau, sig);  // 2 query halves x 2 row halves
     for (int i = tid; i < SD_WAVES * 64 * M; i += SD_WAVES * 64) lists[i] = WVG_KEY_NONE;
     __syncthreads();
     SurvivorLists S;
@@ -1763,7 +1707,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
 
         // loads of one unit (K block ks of a row block): wave w moves the 4 fragments of
         // the block's tile w; with ks = 0 also tile w's norms and errors, and wave 0 the
-        // block's tile words (sd_unit_loads<.., true>)
+        // block's tile words (sd_unit_loads<true>)
         const uint4 *lsrc = a.shadow + ((size_t)(a.tile_begin + blk0 * 4 + w) * KBN * 4) * 64 + lane;
         const float *lnorm = a.norms + (a.tile_begin + blk0 * 4 + w) * 64 + lane;
         const float *lerr = a.errs + (a.tile_begin + blk0 * 4 + w) * 64 + lane;
@@ -1781,15 +1725,8 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
                 __builtin_amdgcn_global_load_lds(lnorm, reinterpret_cast<float *>(nslot + w * 256), 4, 0, 0);
                 __builtin_amdgcn_global_load_lds(lerr, reinterpret_cast<float *>(nslot + 1280 + w * 256), 4, 0, 0);
                 if (w == 0) {
-                    const uint32_t wi = (uint32_t)(lane & 7) >> 1, half = lane & 1;
-                    const uint64_t t = a.tile_begin + lblk * 4 + wi;
-                    const uint32_t *src =
-                        reinterpret_cast<const uint32_t *>(a.valid + (t < a.tile_end ? t : a.tile_end - 1)) + half;
-                    if (lane >= 8 && lane < 16 && a.allow) {
-                        const uint64_t aw = t - a.allow_t0;
-                        src = reinterpret_cast<const uint32_t *>(a.allow + (aw < a.allow_words ? aw : 0)) + half;
-                    }
-                    __builtin_amdgcn_global_load_lds(src, reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
+                    __builtin_amdgcn_global_load_lds(sc_tile_word_src(a, lblk, lane),
+                                                     reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
                 }
             }
             if (ks == KBN - 1 && lblk + 1 < blk1) {  // the load cursor moves on; past the end it stays
@@ -1803,8 +1740,8 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
         // and the NB - 3 younger ones
         auto wait_next = [&](auto KS) {
             constexpr int ks = decltype(KS)::value;
-            constexpr int n0 = sd_younger<KBN, 0, true>(ks + 1, SJ_NB - 3, true);
-            constexpr int n1 = sd_younger<KBN, 0, true>(ks + 1, SJ_NB - 3, false);
+            constexpr int n0 = sd_younger<KBN, true>(ks + 1, SJ_NB - 3, true);
+            constexpr int n1 = sd_younger<KBN, true>(ks + 1, SJ_NB - 3, false);
             if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n0) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n1) : "memory");
         };
@@ -1851,8 +1788,8 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
         // prologue: units 0 .. NB - 2 of the range into buffers 0 .. NB - 2
 #pragma unroll
         for (int ks = 0; ks < SJ_NB - 1; ks++) load_stage(ks % KBN);
-        if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, 0, true>(0, SJ_NB - 2, true)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, 0, true>(0, SJ_NB - 2, false)) : "memory");
+        if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, true>(0, SJ_NB - 2, true)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, true>(0, SJ_NB - 2, false)) : "memory");
         raw_barrier();
         uint32_t cbuf = 0;  // ring buffer of K block 0 of the current row block
         read_half(0u, 0, b0);
@@ -1994,13 +1931,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
                     const uint64_t allows[2] = {((uint64_t)aw.y << 32) | aw.x, ((uint64_t)aw.w << 32) | aw.z};
 #pragma unroll
                     for (int h = 0; h < 2; h++) {
-                        const uint64_t t = a.tile_begin + blk * 4 + 2 * wr + h;
-                        uint64_t m = t < a.tile_end ? readfirstlane64(words[h]) : 0ull;
-                        if (a.allow) {
-                            const uint64_t aw2 = t - a.allow_t0;
-                            m &= aw2 < a.allow_words ? readfirstlane64(allows[h]) : 0ull;
-                        }
-                        vm[h] = m;
+                        vm[h] = sc_tile_mask(a, a.tile_begin + blk * 4 + 2 * wr + h, words[h], allows[h]);
                     }
                 }
                 const uint64_t slot0 = (a.tile_begin + blk * 4 + 2 * wr) * 64;
@@ -2149,1222 +2080,6 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
         }
     }
 }
-
-constexpr int SF_WAVES = 8;  // K3f's waves per workgroup
-
-#ifdef WVG_TOOLS  // K3e and K3f: round-5 A/B variants (tools build only; the product runs K3d)
-// ---------------------------------------------------------------------------
-// K3e (round 5): K3d with 32x32x16 bf16 MFMAs.  K3d's 16x16x32 MFMA takes 16
-// cycles of the matrix pipe and holds the wave's issue for 8 of them, so per
-// 32-deep unit (32 MFMAs, 512 pipe cycles) only ~256 issue cycles are left for
-// the unit's 16 ds_read_b128, 4 LDS-DMA pieces (~60 cycles each among MFMAs,
-// MI355X_MICROARCH.md) and the barrier: one wave per SIMD cannot keep the pipe
-// busy (K3d counters: MFMA busy 40 %).  v_mfma_f32_32x32x16_bf16 does the same
-// work in half the instructions -- 16 per unit, 32 pipe cycles each, 8 of them
-// issue -- which leaves ~384 issue cycles per unit for the same reads, DMA and
-// barrier.  Registers, LDS ring, loads, waits and barriers are K3d's.
-//   A operand = the wave's 32 queries (resident; lane l: query l % 32, k 8 (l / 32) + 0..7
-//   of each 16-deep step -- gathered once from qfrag's 16 x 32 fragments);
-//   B operand = 32 rows of the row block (lane l: row l % 32 of the group, same k),
-//   read straight from the ring's 16 x 32 fragments with a per-lane address
-//   (conflict-free: the 16 lanes of each ds_read_b128 group hit 16 distinct
-//   16-byte bank groups);
-//   C: lane l holds row n = 32 g + (l & 31) of row group g and queries
-//   m = 8 (r >> 2) + 4 (l >> 5) + (r & 3), r = 0..15.
-// Epilogue: per lane and query slot r the largest raw score of its 8 rows +
-// E(its rows' largest norm) against WS (a superset test of every element);
-// one ballot per slot gives 16 wave-uniform bits, each covering two queries
-// (lanes 0-31 and 32-63) x 256 rows; an active slot's two lists sit in lanes
-// 0-15 and 32-47 of one register and survivors are inserted as in K3d.
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-template <int KBN, int DIAG = 0>
-__global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_ar32_kernel(ScreenArgs a)
-{
-    static_assert(KBN % SD_NBUF == 0, "the stage buffer of a K block must be a compile-time constant");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + SD_RING);  // [4][32][M]
-    float *tau = reinterpret_cast<float *>(smem + SD_RING + SD_LISTS);
-    float *sig = tau + SD_WAVES * 32;
-    float *ck1 = sig + SD_WAVES * 32;
-    float *ck2 = ck1 + SD_BQ;
-    float *cem = ck2 + SD_BQ;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int K = (int)a.k, M = SCREEN_M;
-    const int cosine = a.cosine;
-    const uint32_t b = blockIdx.x;
-    uint32_t qb, rr;
-    if (a.nrr_l % 8 == 0) {
-        const uint32_t xcd = b % 8, wv = b / 8;
-        qb = wv % a.nqb;
-        rr = a.rr0 + (wv / a.nqb) * 8 + xcd;
-    } else {
-        qb = b % a.nqb;
-        rr = a.rr0 + b / a.nqb;
-    }
-    const uint64_t ntiles = a.tile_end - a.tile_begin;
-    const uint64_t nblk = (ntiles + 3) / 4;
-    const uint64_t blk0 = nblk * rr / a.nrr, blk1 = nblk * (rr + 1) / a.nrr;
-    const uint32_t q0 = qb * SD_BQ;
-
-    for (int i = tid; i < SD_BQ; i += SD_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        ck1[i] = a.k1[q];
-        ck2[i] = a.k2[q];
-        cem[i] = a.emax[q];
-    }
-    for (int i = tid; i < SD_WAVES * 32; i += SD_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        const uint32_t g = q < a.nq ? __hip_atomic_load(a.gbound + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const float t = q >= a.nq ? -__builtin_inff() : (g == 0xFFFFFFFFu ? __builtin_inff() : wvg_unord_f32(g));
-        tau[i] = t;
-        sig[i] = q >= a.nq ? __builtin_inff() : sc_sigma(t, cosine);
-    }
-    for (int i = tid; i < SD_WAVES * 32 * M; i += SD_WAVES * 64) lists[i] = WVG_KEY_NONE;
-    __syncthreads();
-    const uint32_t laddr = (uint32_t)(uintptr_t)(lists + (size_t)w * 32 * M);
-    const uint32_t tbase = (uint32_t)(uintptr_t)(tau + w * 32);
-    if (blk0 < blk1) {
-        // the wave's 32 queries, every K block and step, resident for the whole range
-        bf16x8 areg[KBN][2];
-        constexpr int SD_AKB = 6;  // K blocks whose fragments live in AGPRs (as K3d)
-        {
-            const uint32_t ql = (uint32_t)lane & 31u;
-            const uint4 *qsrc = a.qfrag + (size_t)(qb * 8 + 2 * w + (ql >> 4)) * KBN * 64 + (ql & 15u);
-#pragma unroll
-            for (int ks = 0; ks < KBN; ks++)
-#pragma unroll
-                for (int st = 0; st < 2; st++) {
-                    const uint4 *src = qsrc + (size_t)ks * 64 + (2 * st + (lane >> 5)) * 16;
-                    if (ks < SD_AKB)
-                        asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(areg[ks][st]) : "v"(src) : "memory");
-                    else
-                        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(areg[ks][st]) : "v"(src) : "memory");
-                }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int ks = 0; ks < KBN; ks++)
-#pragma unroll
-            for (int st = 0; st < 2; st++) {
-                if (ks < SD_AKB)
-                    asm volatile("" : "+a"(areg[ks][st]));
-                else
-                    asm volatile("" : "+v"(areg[ks][st]));
-            }
-
-        // the stage loads: K3d's (wave w moves tile w's four 16-row fragments; unit 0 also
-        // its norms, wave 0 the block's tile words)
-        const uint4 *lsrc = a.shadow + ((size_t)(a.tile_begin + blk0 * 4 + w) * KBN * 4) * 64 + lane;
-        const float *lnorm = a.norms + (a.tile_begin + blk0 * 4 + w) * 64 + lane;
-        uint64_t lblk = blk0;
-        auto load_stage = [&](int ks) {
-            unsigned char *dst = smem + (ks % SD_NBUF) * SD_STAGE;
-#pragma unroll
-            for (int rg = 0; rg < 4; rg++)
-                __builtin_amdgcn_global_load_lds(lsrc + ((size_t)ks * 4 + rg) * 64,
-                                                 reinterpret_cast<uint4 *>(dst + (4 * w + rg) * 1024), 16, 0, 0);
-            unsigned char *nslot = smem + SD_NBUF * SD_STAGE + (lblk & 1) * SD_NSLOT;
-            if (ks == 0)
-                __builtin_amdgcn_global_load_lds(lnorm, reinterpret_cast<float *>(nslot + w * 256), 4, 0, 0);
-            if (ks == 0 && w == 0) {
-                const uint32_t wi = (uint32_t)(lane & 7) >> 1, half = lane & 1;
-                const uint64_t t = a.tile_begin + lblk * 4 + wi;
-                const uint32_t *src =
-                    reinterpret_cast<const uint32_t *>(a.valid + (t < a.tile_end ? t : a.tile_end - 1)) + half;
-                if (lane >= 8 && lane < 16 && a.allow) {
-                    const uint64_t aw = t - a.allow_t0;
-                    src = reinterpret_cast<const uint32_t *>(a.allow + (aw < a.allow_words ? aw : 0)) + half;
-                }
-                __builtin_amdgcn_global_load_lds(src, reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
-            }
-            if (ks == KBN - 1 && lblk + 1 < blk1) {
-                ++lblk;
-                lsrc += (size_t)4 * KBN * 4 * 64;
-                lnorm += 256;
-            }
-        };
-        auto wait_next = [&](auto KS) {
-            constexpr int ks = decltype(KS)::value;
-            constexpr int n0 = sd_younger<KBN, 0>(ks + 1, SD_NBUF - 3, true);
-            constexpr int n1 = sd_younger<KBN, 0>(ks + 1, SD_NBUF - 3, false);
-            if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n0) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n1) : "memory");
-        };
-        auto raw_barrier = [&]() {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        };
-        // B fragments of step st (8 row groups of 32) straight into AGPRs: lane l reads row
-        // l % 32 of group g, k 8 (2 st + l / 32) .. + 7 of the unit, i.e. 16-row fragment
-        // 2 g + ((l & 31) >> 4), lane (2 st + l / 32) * 16 + (l & 15) of it
-        const uint32_t rbase = (uint32_t)(uintptr_t)smem + (uint32_t)(lane >> 5) * 256u +
-                               (uint32_t)((lane & 31) >> 4) * 1024u + (uint32_t)(lane & 15) * 16u;
-        auto read_half = [&](int ks, int st, bf16x8 (&br)[8]) {
-            const uint32_t soff = (uint32_t)((ks % SD_NBUF) * SD_STAGE + st * 512);
-            uint32_t tmp;
-            asm volatile("v_add_u32 %8, %9, %10\n\t"
-                         "ds_read_b128 %0, %8\n\t"
-                         "ds_read_b128 %1, %8 offset:2048\n\t"
-                         "ds_read_b128 %2, %8 offset:4096\n\t"
-                         "ds_read_b128 %3, %8 offset:6144\n\t"
-                         "ds_read_b128 %4, %8 offset:8192\n\t"
-                         "ds_read_b128 %5, %8 offset:10240\n\t"
-                         "ds_read_b128 %6, %8 offset:12288\n\t"
-                         "ds_read_b128 %7, %8 offset:14336"
-                         : "=a"(br[0]), "=a"(br[1]), "=a"(br[2]), "=a"(br[3]), "=a"(br[4]), "=a"(br[5]), "=a"(br[6]),
-                           "=a"(br[7]), "=&v"(tmp)
-                         : "s"(soff), "v"(rbase)
-                         : "memory");
-        };
-        auto wait_b0 = [&](bf16x8 (&br)[8]) {
-            asm volatile("s_waitcnt lgkmcnt(8)"
-                         : "+a"(br[0]), "+a"(br[1]), "+a"(br[2]), "+a"(br[3]), "+a"(br[4]), "+a"(br[5]), "+a"(br[6]),
-                           "+a"(br[7])
-                         :
-                         : "memory");
-        };
-        // this lane's queries: m(r) = 8 (r >> 2) + qh + (r & 3), qh = 4 (l >> 5)
-        const int qh = 4 * (lane >> 5);
-        const uint32_t sbase = (uint32_t)(uintptr_t)smem;
-        const uint32_t nbase = sbase + 4u * (uint32_t)(lane & 31);  // norm of row 32 g + (l & 31): + 128 g
-        const uint32_t csoff = (uint32_t)((uintptr_t)sig - (uintptr_t)smem);
-        bool lane_force = false;
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-            if (!(ck1[32 * w + 8 * (r >> 2) + qh + (r & 3)] <= 0x1p50f)) lane_force = true;
-
-        floatx16 acc[8];
-#pragma unroll
-        for (int g = 0; g < 8; g++)
-#pragma unroll
-            for (int e = 0; e < 16; e++) acc[g][e] = 0.f;
-        bf16x8 b0[8], b1[8];
-#pragma unroll
-        for (int ks = 0; ks < SD_NBUF - 1; ks++) load_stage(ks);
-        if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, 0>(0, SD_NBUF - 2, true)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, 0>(0, SD_NBUF - 2, false)) : "memory");
-        raw_barrier();
-        read_half(0, 0, b0);
-        for (uint64_t blk = blk0; blk < blk1; blk++) {
-            sd_static_for<KBN>([&](auto KS) {
-                constexpr int ks = decltype(KS)::value;
-                read_half(ks, 1, b1);
-                wait_b0(b0);
-#pragma unroll
-                for (int g = 0; g < 8; g++)
-                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(areg[ks][0], b0[g], acc[g], 0, 0, 0);
-                wait_next(KS);
-                raw_barrier();  // (lgkmcnt(0): this wave's second-step reads done)
-#pragma unroll
-                for (int j = 0; j < 8; j++) asm volatile("" : "+a"(b1[j]));
-                load_stage((ks + SD_NBUF - 1) % KBN);  // unit + 7 into the buffer of unit - 1
-                if (ks + 1 < KBN) read_half(ks + 1, 0, b0);
-#pragma unroll
-                for (int g = 0; g < 8; g++)
-                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(areg[ks][1], b1[g], acc[g], 0, 0, 0);
-            });
-            // 32x32x16: 16 passes, 18 wait states before a VALU reads its result (agpr_read
-            // is inline asm the hazard recognizer does not see)
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr ((DIAG & 2) == 0) {
-                const uint32_t nsoff = (uint32_t)(SD_NBUF * SD_STAGE + (blk & 1) * SD_NSLOT);
-                float nrm[8];
-                {
-                    uint32_t tmp;
-                    asm volatile("v_add_u32 %8, %9, %10\n\t"
-                                 "ds_read_b32 %0, %8\n\t"
-                                 "ds_read_b32 %1, %8 offset:128\n\t"
-                                 "ds_read_b32 %2, %8 offset:256\n\t"
-                                 "ds_read_b32 %3, %8 offset:384\n\t"
-                                 "ds_read_b32 %4, %8 offset:512\n\t"
-                                 "ds_read_b32 %5, %8 offset:640\n\t"
-                                 "ds_read_b32 %6, %8 offset:768\n\t"
-                                 "ds_read_b32 %7, %8 offset:896\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=v"(nrm[0]), "=v"(nrm[1]), "=v"(nrm[2]), "=v"(nrm[3]), "=v"(nrm[4]),
-                                   "=v"(nrm[5]), "=v"(nrm[6]), "=v"(nrm[7]), "=&v"(tmp)
-                                 : "s"(nsoff), "v"(nbase)
-                                 : "memory");
-                }
-                float nmax = nrm[0], nsum = nrm[0];
-#pragma unroll
-                for (int g = 1; g < 8; g++) nmax = __builtin_fmaxf(nmax, nrm[g]), nsum += nrm[g];
-                const bool force = lane_force || !(nmax <= 0x1p60f) || nsum != nsum;
-                uint32_t wact = 0;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    // queries 32 w + 8 i + qh + 0..3: sig, ck1, ck2 (128-float arrays, +512 / +1024 B)
-                    const uint32_t coff = (uint32_t)(csoff + 4 * (32 * w + 8 * i));
-                    const uint32_t qbase = sbase + 4u * (uint32_t)qh;
-                    float4 k1v, k2v, sv;
-                    uint32_t tmp;
-                    asm volatile("v_add_u32 %3, %4, %5\n\t"
-                                 "ds_read_b128 %0, %3 offset:512\n\t"
-                                 "ds_read_b128 %1, %3 offset:1024\n\t"
-                                 "ds_read_b128 %2, %3\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=v"(k1v), "=v"(k2v), "=v"(sv), "=&v"(tmp)
-                                 : "s"(coff), "v"(qbase)
-                                 : "memory");
-                    const float k1r[4] = {k1v.x, k1v.y, k1v.z, k1v.w}, k2r[4] = {k2v.x, k2v.y, k2v.z, k2v.w};
-                    const float svr[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const int r = 4 * i + j;
-                        float m = agpr_read(acc[0][r]);
-#pragma unroll
-                        for (int g = 1; g < 8; g++) m = __builtin_fmaxf(m, agpr_read(acc[g][r]));
-                        const float t = (m + __builtin_fmaf(nmax, k1r[j], k2r[j])) - svr[j];
-                        if (__ballot(force || t >= 0.f)) wact |= 1u << r;
-                    }
-                }
-                if (wact != 0 && (DIAG & 4) == 0) {
-                    uint64_t vm[4];
-                    {
-                        uint4 vw0, vw1, aw0, aw1;
-                        uint32_t tmp;
-                        asm volatile("v_add_u32 %4, %5, %6\n\t"
-                                     "ds_read_b128 %0, %4 offset:1024\n\t"
-                                     "ds_read_b128 %1, %4 offset:1040\n\t"
-                                     "ds_read_b128 %2, %4 offset:1056\n\t"
-                                     "ds_read_b128 %3, %4 offset:1072\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=v"(vw0), "=v"(vw1), "=v"(aw0), "=v"(aw1), "=&v"(tmp)
-                                     : "s"(nsoff), "v"(sbase)
-                                     : "memory");
-                        const uint64_t words[4] = {((uint64_t)vw0.y << 32) | vw0.x, ((uint64_t)vw0.w << 32) | vw0.z,
-                                                   ((uint64_t)vw1.y << 32) | vw1.x, ((uint64_t)vw1.w << 32) | vw1.z};
-                        const uint64_t allows[4] = {((uint64_t)aw0.y << 32) | aw0.x, ((uint64_t)aw0.w << 32) | aw0.z,
-                                                    ((uint64_t)aw1.y << 32) | aw1.x, ((uint64_t)aw1.w << 32) | aw1.z};
-#pragma unroll
-                        for (int h = 0; h < 4; h++) {
-                            const uint64_t t = a.tile_begin + blk * 4 + h;
-                            uint64_t m = t < a.tile_end ? readfirstlane64(words[h]) : 0ull;
-                            if (a.allow) {
-                                const uint64_t aw = t - a.allow_t0;
-                                m &= aw < a.allow_words ? readfirstlane64(allows[h]) : 0ull;
-                            }
-                            vm[h] = m;
-                        }
-                    }
-                    const uint64_t slot0 = (a.tile_begin + blk * 4) * 64;
-                    // live rows of each row group g (lane l: row 32 g + (l & 31))
-                    uint64_t live[8];
-#pragma unroll
-                    for (int g = 0; g < 8; g++)
-                        live[g] = __ballot((vm[g >> 1] >> (32 * (g & 1) + (lane & 31))) & 1ull);
-                    const int li = lane & 15;
-                    for (uint32_t gw = wact; gw; gw &= gw - 1) {
-                        const int r = __builtin_ctz(gw);
-                        float uv[8];
-                        switch (r) {
-#define WVG_SE_SLOT(R)                                                                          \
-    case R:                                                                                     \
-        _Pragma("unroll") for (int g = 0; g < 8; g++) uv[g] = agpr_read(acc[g][R]);           \
-        break;
-                        WVG_SE_SLOT(0) WVG_SE_SLOT(1) WVG_SE_SLOT(2) WVG_SE_SLOT(3)
-                        WVG_SE_SLOT(4) WVG_SE_SLOT(5) WVG_SE_SLOT(6) WVG_SE_SLOT(7)
-                        WVG_SE_SLOT(8) WVG_SE_SLOT(9) WVG_SE_SLOT(10) WVG_SE_SLOT(11)
-                        WVG_SE_SLOT(12) WVG_SE_SLOT(13) WVG_SE_SLOT(14) WVG_SE_SLOT(15)
-#undef WVG_SE_SLOT
-                        default: break;
-                        }
-                        const uint32_t ql = 8u * (uint32_t)(r >> 2) + (uint32_t)qh + (uint32_t)(r & 3);
-                        const uint32_t la = laddr + ql * (SCREEN_M * 8) + 8u * (uint32_t)li;
-                        const uint32_t ta = tbase + 4u * ql;  // tau; sig + 512, ck1 + 1024, ck2 + 1536, cem + 2048
-                        uint2 v2;
-                        float wt, ws, em, k1, k2;
-                        asm volatile("ds_read_b64 %0, %6\n\t"
-                                     "ds_read_b32 %1, %7\n\t"
-                                     "ds_read_b32 %2, %7 offset:512\n\t"
-                                     "ds_read_b32 %3, %7 offset:2048\n\t"
-                                     "ds_read_b32 %4, %7 offset:1024\n\t"
-                                     "ds_read_b32 %5, %7 offset:1536\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=v"(v2), "=v"(wt), "=v"(ws), "=v"(em), "=v"(k1), "=v"(k2)
-                                     : "v"(la), "v"(ta)
-                                     : "memory");
-                        uint64_t v = ((uint64_t)v2.y << 32) | v2.x;
-#pragma unroll
-                        for (int g = 0; g < 8; g++) {
-                            const float u = uv[g] + __builtin_fmaf(nrm[g], k1, k2);
-                            uint64_t pass = __ballot(!(u < ws)) & live[g];
-                            while (pass) {
-                                const int j = __builtin_ctzll(pass);
-                                pass &= pass - 1;
-                                const int gr = 2 * (j >> 5);  // the survivor's query's list row
-                                const float lower =
-                                    sc_lower(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j)), cosine);
-                                float wtg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wt), j));
-                                if (!(lower <= wtg)) continue;
-                                const uint64_t key = ((uint64_t)wvg_ord_f32(lower) << 32) |
-                                                     (uint32_t)(slot0 + 32u * (uint32_t)g + (uint32_t)(j & 31));
-                                if (!(key < readlane64(v, 16 * gr + SCREEN_M - 1))) continue;
-                                const bool inrow = (lane >> 4) == gr;
-                                const int pos = __popcll(__ballot(inrow && v < key));
-                                const uint64_t sh = row_shr1_64(v);
-                                v = inrow ? (li > pos ? sh : (li == pos ? key : v)) : v;
-                                const uint64_t nk = readlane64(v, 16 * gr + K - 1);
-                                const uint64_t nm = readlane64(v, 16 * gr + SCREEN_M - 1);
-                                const float emg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(em), j));
-                                if (nk != WVG_KEY_NONE) wtg = fminf(wtg, sc_tau_k(key_lower(nk), emg, cosine));
-                                if (nm != WVG_KEY_NONE) wtg = fminf(wtg, key_lower(nm));
-                                const float wsg = sc_sigma(wtg, cosine);
-                                const bool mine = (lane >> 5) == (j >> 5);  // lanes of the survivor's query
-                                wt = mine ? wtg : wt;
-                                ws = mine ? wsg : ws;
-                                // that query's other survivors of this row group meet the new threshold
-                                pass &= ~(0xFFFFFFFFull << (32 * (j >> 5))) | __ballot(!(u < ws));
-                            }
-                        }
-                        const uint2 o2 = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-                        if (((lane >> 4) & 1) == 0) asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(o2) : "memory");
-                        if ((lane & 31) == 0)
-                            asm volatile("ds_write_b32 %0, %1\n\t"
-                                         "ds_write_b32 %0, %2 offset:512" ::"v"(ta), "v"(wt), "v"(ws)
-                                         : "memory");
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                }
-            } else if constexpr ((DIAG & 8) != 0) {
-                float x = 0.f;
-#pragma unroll
-                for (int g = 0; g < 8; g++) x += agpr_read(acc[g][0]);
-                if (x == 0x1p-120f) a.partials[0] = 0;
-            }
-#pragma unroll
-            for (int g = 0; g < 8; g++)
-#pragma unroll
-                for (int e = 0; e < 16; e++) acc[g][e] = 0.f;
-            read_half(0, 0, b0);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int ql = 0; ql < 32; ql++) {
-        const uint32_t q = q0 + (uint32_t)(32 * w + ql);
-        if (q >= a.nq) break;
-        const uint64_t x = lane < M ? lists[((size_t)w * 32 + ql) * M + lane] : WVG_KEY_NONE;
-        uint64_t *out = a.partials + ((size_t)q * a.nrr + rr) * M;
-        if (lane < M) out[lane] = x;
-        if (lane == K - 1 && x != WVG_KEY_NONE) {
-            const float t = sc_tau_k(key_lower(x), cem[32 * w + ql], cosine);
-            atomicMin(a.gbound + q, wvg_ord_f32(t));
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// K3f (round 5): K3d at two waves per SIMD.  K3d's counters (profiles/r05/k3e)
-// put the matrix pipe at 43 % busy: per 32-deep unit its one wave per SIMD
-// spends 512 cycles issuing MFMAs and, serially after them, the barrier, four
-// LDS-DMA pieces (~60 cycles of issue each) and 16 ds_read_b128 -- ~1180
-// cycles per unit.  K3e's fewer, longer MFMAs left that unchanged.  K3f keeps
-// 128 queries per workgroup but gives each of 8 waves 16 of them (96 resident
-// AGPRs, 64 accumulator AGPRs, 32 for a quarter-stage double buffer), so a SIMD
-// holds two waves and one wave's DMA issue, barrier wait and reads overlap the
-// other's MFMAs.  The price is LDS traffic: every wave reads the whole stage,
-// 128 KiB of ds_read_b128 + 16 KiB of DMA per unit per CU = 576 LDS-array
-// cycles at 256 B/clk against 512 MFMA cycles per SIMD -- the LDS, not the
-// issue stream, bounds the loop.  Ring, loads (2 pieces per wave), waits,
-// epilogue tests and lists are K3d's; lists and thresholds keep K3d's LDS
-// layout (wave w owns queries 16 w .. 16 w + 15 of the workgroup's 128).
-static_assert(SF_WAVES * 16 == SD_BQ && SD_WAVES * 32 == SD_BQ, "K3f keeps K3d's 128-query LDS layout");
-
-// Vector-memory loads one K3f wave issues for unit u: its 2 row-fragment
-// pieces; with unit 0 waves 4..7 also the norms of tile w - 4 and wave 0 the
-// block's tile words (ex: a wave with that extra load).
-constexpr int sf_unit_loads(int u, bool ex)
-{
-    return 2 + (u == 0 && ex ? 1 : 0);
-}
-template <int KBN>
-constexpr int sf_younger(int first, int n, bool ex)
-{
-    int c = 0;
-    for (int i = 1; i <= n; i++) c += sf_unit_loads((first + i) % KBN, ex);
-    return c;
-}
-
-template <int KBN, int DIAG = 0>
-__global__ __launch_bounds__(SF_WAVES * 64) void screen_ar16_kernel(ScreenArgs a)
-{
-    static_assert(KBN % SD_NBUF == 0, "the stage buffer of a K block must be a compile-time constant");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + SD_RING);  // [8][16][M]
-    float *tau = reinterpret_cast<float *>(smem + SD_RING + SD_LISTS);
-    float *sig = tau + SD_BQ;
-    float *ck1 = sig + SD_BQ;
-    float *ck2 = ck1 + SD_BQ;
-    float *cem = ck2 + SD_BQ;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int K = (int)a.k, M = SCREEN_M;
-    const int cosine = a.cosine;
-    const uint32_t b = blockIdx.x;
-    uint32_t qb, rr;
-    if (a.nrr_l % 8 == 0) {
-        const uint32_t xcd = b % 8, wv = b / 8;
-        qb = wv % a.nqb;
-        rr = a.rr0 + (wv / a.nqb) * 8 + xcd;
-    } else {
-        qb = b % a.nqb;
-        rr = a.rr0 + b / a.nqb;
-    }
-    const uint64_t ntiles = a.tile_end - a.tile_begin;
-    const uint64_t nblk = (ntiles + 3) / 4;
-    const uint64_t blk0 = nblk * rr / a.nrr, blk1 = nblk * (rr + 1) / a.nrr;
-    const uint32_t q0 = qb * SD_BQ;
-
-    for (int i = tid; i < SD_BQ; i += SF_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        ck1[i] = a.k1[q];
-        ck2[i] = a.k2[q];
-        cem[i] = a.emax[q];
-        const uint32_t g = q < a.nq ? __hip_atomic_load(a.gbound + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const float t = q >= a.nq ? -__builtin_inff() : (g == 0xFFFFFFFFu ? __builtin_inff() : wvg_unord_f32(g));
-        tau[i] = t;
-        sig[i] = q >= a.nq ? __builtin_inff() : sc_sigma(t, cosine);
-    }
-    for (int i = tid; i < SD_BQ * M; i += SF_WAVES * 64) lists[i] = WVG_KEY_NONE;
-    __syncthreads();
-    const uint32_t laddr = (uint32_t)(uintptr_t)(lists + (size_t)w * 16 * M);
-    const uint32_t tbase = (uint32_t)(uintptr_t)(tau + w * 16);  // sig + 512, ck1 + 1024, ck2 + 1536, cem + 2048
-    const bool ex = w == 0 || w >= 4;
-    if (blk0 < blk1) {
-        // the wave's 16 queries, every K block, resident for the whole range: the
-        // compiler splits a 256-register wave's file 128 / 128 between VGPRs and
-        // AGPRs, so the first SF_AKB K blocks sit next to the accumulators (64) and
-        // the quarter buffers (32) in AGPRs, the rest in VGPRs
-        constexpr int SF_AKB = 8;
-        bf16x8 areg[KBN];
-        {
-            const uint4 *qsrc = a.qfrag + (size_t)(qb * 8 + w) * KBN * 64 + lane;
-#pragma unroll
-            for (int ks = 0; ks < KBN; ks++) {
-                if (ks < SF_AKB)
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(areg[ks]) : "v"(qsrc + (size_t)ks * 64) : "memory");
-                else
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(areg[ks]) : "v"(qsrc + (size_t)ks * 64) : "memory");
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int ks = 0; ks < KBN; ks++) {
-                if (ks < SF_AKB)
-                    asm volatile("" : "+a"(areg[ks]));
-                else
-                    asm volatile("" : "+v"(areg[ks]));
-            }
-        }
-        // loads of one stage: wave w moves row fragments 2 w, 2 w + 1 (tile w / 2, row
-        // groups 2 (w & 1) + 0, 1); with unit 0 waves 4..7 the norms of tile w - 4 and
-        // wave 0 the block's tile words (sf_unit_loads)
-        // (wave-uniform bases + the lane: SGPR base + lane offset, no per-lane 64-bit pointers)
-        const uint4 *lsrc = a.shadow + ((size_t)(a.tile_begin + blk0 * 4 + (w >> 1)) * KBN * 4) * 64;
-        const float *lnorm = a.norms + (a.tile_begin + blk0 * 4 + (w & 3)) * 64;
-        const int rg0 = 2 * (w & 1);
-        uint64_t lblk = blk0;
-        auto load_stage = [&](int ks) {
-            unsigned char *dst = smem + (ks % SD_NBUF) * SD_STAGE;
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-                __builtin_amdgcn_global_load_lds(lsrc + ((size_t)ks * 4 + rg0 + j) * 64 + lane,
-                                                 reinterpret_cast<uint4 *>(dst + (2 * w + j) * 1024), 16, 0, 0);
-            unsigned char *nslot = smem + SD_NBUF * SD_STAGE + (lblk & 1) * SD_NSLOT;
-            if (ks == 0 && w >= 4)
-                __builtin_amdgcn_global_load_lds(lnorm + lane, reinterpret_cast<float *>(nslot + (w - 4) * 256), 4, 0,
-                                                 0);
-            if (ks == 0 && w == 0) {
-                const uint32_t wi = (uint32_t)(lane & 7) >> 1, half = lane & 1;
-                const uint64_t t = a.tile_begin + lblk * 4 + wi;
-                const uint32_t *src =
-                    reinterpret_cast<const uint32_t *>(a.valid + (t < a.tile_end ? t : a.tile_end - 1)) + half;
-                if (lane >= 8 && lane < 16 && a.allow) {
-                    const uint64_t aw = t - a.allow_t0;
-                    src = reinterpret_cast<const uint32_t *>(a.allow + (aw < a.allow_words ? aw : 0)) + half;
-                }
-                __builtin_amdgcn_global_load_lds(src, reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
-            }
-            if (ks == KBN - 1 && lblk + 1 < blk1) {  // the load cursor moves on; past the end it stays
-                ++lblk;
-                lsrc += (size_t)4 * KBN * 4 * 64;
-                lnorm += 256;
-            }
-        };
-        // six stages in flight at every wait (K3d's ring): unit ks + 1 landed, the
-        // loads of units ks + 2 .. ks + 6 left outstanding
-        auto wait_next = [&](auto KS) {
-            constexpr int ks = decltype(KS)::value;
-            constexpr int n1 = sf_younger<KBN>(ks + 1, SD_NBUF - 3, true);
-            constexpr int n0 = sf_younger<KBN>(ks + 1, SD_NBUF - 3, false);
-            if (ex) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n1) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n0) : "memory");
-        };
-        auto raw_barrier = [&]() {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        };
-        // A quarter stage (row fragments 4 qq .. 4 qq + 3) straight into AGPRs, in
-        // flight while the previous quarter's MFMAs issue; consumers pass wait_q
-        // (lgkmcnt(4): every read but the 4 younger ones landed) or the barrier.
-        // The stage / quarter offset is an instruction literal (as SGPR operands the
-        // 32 distinct offsets were hoisted into SGPRs and spilled).
-        const uint32_t rbase = (uint32_t)(uintptr_t)smem + 16u * lane;
-        auto read_q = [](auto KS, auto QQ, bf16x8 (&br)[4], uint32_t rb) {
-            constexpr uint32_t soff =
-                (uint32_t)((decltype(KS)::value % SD_NBUF) * SD_STAGE + decltype(QQ)::value * 4 * 1024);
-            uint32_t tmp;
-            asm volatile("v_add_u32 %4, %5, %6\n\t"
-                         "ds_read_b128 %0, %4\n\t"
-                         "ds_read_b128 %1, %4 offset:1024\n\t"
-                         "ds_read_b128 %2, %4 offset:2048\n\t"
-                         "ds_read_b128 %3, %4 offset:3072"
-                         : "=a"(br[0]), "=a"(br[1]), "=a"(br[2]), "=a"(br[3]), "=&v"(tmp)
-                         : "n"(soff), "v"(rb)
-                         : "memory");
-        };
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
-        using I3 = std::integral_constant<int, 3>;
-        auto wait_q = [&](bf16x8 (&br)[4]) {
-            asm volatile("s_waitcnt lgkmcnt(4)" : "+a"(br[0]), "+a"(br[1]), "+a"(br[2]), "+a"(br[3]) : : "memory");
-        };
-        const int qlane = 4 * (lane >> 4);
-        const uint32_t sbase = (uint32_t)(uintptr_t)smem;
-        const uint32_t nbase = sbase + 4u * (uint32_t)(lane & 15);
-        const uint32_t qbase = sbase + 4u * (uint32_t)qlane;
-        const uint32_t csoff = (uint32_t)((uintptr_t)sig - (uintptr_t)smem);
-        bool lane_force = false;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            if (!(ck1[16 * w + qlane + r] <= 0x1p50f)) lane_force = true;
-
-        floatx4 acc[16];
-#pragma unroll
-        for (int nr = 0; nr < 16; nr++) acc[nr] = (floatx4){0.f, 0.f, 0.f, 0.f};
-        bf16x8 bq0[4], bq1[4];
-        auto mfma4 = [&](int ks, int qq, bf16x8 (&br)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                acc[4 * qq + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(areg[ks], br[j], acc[4 * qq + j], 0, 0, 0);
-        };
-#pragma unroll
-        for (int ks = 0; ks < SD_NBUF - 1; ks++) load_stage(ks);
-        if (ex) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sf_younger<KBN>(0, SD_NBUF - 2, true)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sf_younger<KBN>(0, SD_NBUF - 2, false)) : "memory");
-        raw_barrier();
-        read_q(I0{}, I0{}, bq0, rbase);
-        for (uint64_t blk = blk0; blk < blk1; blk++) {
-            sd_static_for<KBN>([&](auto KS) {
-                constexpr int ks = decltype(KS)::value;
-                read_q(KS, I1{}, bq1, rbase);
-                wait_q(bq0);
-                mfma4(ks, 0, bq0);
-                read_q(KS, I2{}, bq0, rbase);
-                wait_q(bq1);
-                mfma4(ks, 1, bq1);
-                read_q(KS, I3{}, bq1, rbase);
-                wait_q(bq0);
-                mfma4(ks, 2, bq0);
-                wait_next(KS);  // the next unit landed
-                raw_barrier();  // (lgkmcnt(0): quarter 3 landed)
-#pragma unroll
-                for (int j = 0; j < 4; j++) asm volatile("" : "+a"(bq1[j]));
-                load_stage((ks + SD_NBUF - 1) % KBN);  // into the buffer of unit - 1, read before the barrier
-                if constexpr (ks + 1 < KBN) read_q(std::integral_constant<int, ks + 1>{}, I0{}, bq0, rbase);
-                mfma4(ks, 3, bq1);
-            });
-            // XDL write -> VALU read of the accumulators through agpr_read: see K3d
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr ((DIAG & 2) == 0) {
-                // K3d's epilogue over the wave's 16 queries: C layout row (query) qlane + r,
-                // column (row) 16 nr + (lane & 15); fast check per query r, exact test on
-                // the groups it could not rule out
-                const uint32_t nsoff = (uint32_t)(SD_NBUF * SD_STAGE + (blk & 1) * SD_NSLOT);
-                auto read_norms8 = [&](int hh, float (&nrm)[8]) {
-                    uint32_t tmp;
-                    asm volatile("v_add_u32 %8, %9, %10\n\t"
-                                 "ds_read_b32 %0, %8\n\t"
-                                 "ds_read_b32 %1, %8 offset:64\n\t"
-                                 "ds_read_b32 %2, %8 offset:128\n\t"
-                                 "ds_read_b32 %3, %8 offset:192\n\t"
-                                 "ds_read_b32 %4, %8 offset:256\n\t"
-                                 "ds_read_b32 %5, %8 offset:320\n\t"
-                                 "ds_read_b32 %6, %8 offset:384\n\t"
-                                 "ds_read_b32 %7, %8 offset:448\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=v"(nrm[0]), "=v"(nrm[1]), "=v"(nrm[2]), "=v"(nrm[3]), "=v"(nrm[4]),
-                                   "=v"(nrm[5]), "=v"(nrm[6]), "=v"(nrm[7]), "=&v"(tmp)
-                                 : "s"(nsoff + 512u * hh), "v"(nbase)
-                                 : "memory");
-                };
-                float nmax, nsum;
-                {
-                    float n0[8], n1[8];
-                    read_norms8(0, n0);
-                    read_norms8(1, n1);
-                    nmax = n0[0];
-                    nsum = n0[0];
-#pragma unroll
-                    for (int j2 = 1; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n0[j2]), nsum += n0[j2];
-#pragma unroll
-                    for (int j2 = 0; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n1[j2]), nsum += n1[j2];
-                }
-                const bool force = lane_force || !(nmax <= 0x1p60f) || nsum != nsum;
-                uint32_t wact = 0;
-                {
-                    const uint32_t coff = (uint32_t)(csoff + 4 * (16 * w));
-                    float4 k1v, k2v, sv;
-                    uint32_t tmp;
-                    asm volatile("v_add_u32 %3, %4, %5\n\t"
-                                 "ds_read_b128 %0, %3 offset:512\n\t"
-                                 "ds_read_b128 %1, %3 offset:1024\n\t"
-                                 "ds_read_b128 %2, %3\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=v"(k1v), "=v"(k2v), "=v"(sv), "=&v"(tmp)
-                                 : "s"(coff), "v"(qbase)
-                                 : "memory");
-                    const float k1r[4] = {k1v.x, k1v.y, k1v.z, k1v.w};
-                    const float k2r[4] = {k2v.x, k2v.y, k2v.z, k2v.w};
-                    const float svr[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        float m = agpr_read(acc[0][r]);
-#pragma unroll
-                        for (int nr = 1; nr < 16; nr++) m = __builtin_fmaxf(m, agpr_read(acc[nr][r]));
-                        const float t = (m + __builtin_fmaf(nmax, k1r[r], k2r[r])) - svr[r];
-                        if (__ballot(force || t >= 0.f)) wact |= 1u << r;
-                    }
-                }
-                if (wact != 0) {
-                    uint64_t vm[4];
-                    {
-                        uint4 vw0, vw1, aw0, aw1;
-                        uint32_t tmp;
-                        asm volatile("v_add_u32 %4, %5, %6\n\t"
-                                     "ds_read_b128 %0, %4 offset:1024\n\t"
-                                     "ds_read_b128 %1, %4 offset:1040\n\t"
-                                     "ds_read_b128 %2, %4 offset:1056\n\t"
-                                     "ds_read_b128 %3, %4 offset:1072\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=v"(vw0), "=v"(vw1), "=v"(aw0), "=v"(aw1), "=&v"(tmp)
-                                     : "s"(nsoff), "v"(sbase)
-                                     : "memory");
-                        const uint64_t words[4] = {((uint64_t)vw0.y << 32) | vw0.x, ((uint64_t)vw0.w << 32) | vw0.z,
-                                                   ((uint64_t)vw1.y << 32) | vw1.x, ((uint64_t)vw1.w << 32) | vw1.z};
-                        const uint64_t allows[4] = {((uint64_t)aw0.y << 32) | aw0.x, ((uint64_t)aw0.w << 32) | aw0.z,
-                                                    ((uint64_t)aw1.y << 32) | aw1.x, ((uint64_t)aw1.w << 32) | aw1.z};
-#pragma unroll
-                        for (int h = 0; h < 4; h++) {
-                            const uint64_t t = a.tile_begin + blk * 4 + h;
-                            uint64_t m = t < a.tile_end ? readfirstlane64(words[h]) : 0ull;
-                            if (a.allow) {
-                                const uint64_t aw = t - a.allow_t0;
-                                m &= aw < a.allow_words ? readfirstlane64(allows[h]) : 0ull;
-                            }
-                            vm[h] = m;
-                        }
-                    }
-                    const uint64_t slot0 = (a.tile_begin + blk * 4) * 64;
-                    // per active query slot gi: lane l tests its column's 16 rows against query
-                    // qlane + gi, and row l >> 4 of v holds that query's list (K3d's slow path;
-                    // four groups, each its own unrolled copy reading its accumulators in place)
-                    sd_static_for<4>([&](auto G) {
-                        constexpr int gi = decltype(G)::value;
-                        if (((wact >> gi) & 1u) == 0) return;
-                        const uint32_t ql = (uint32_t)gi + (uint32_t)qlane;
-                        const uint32_t la = laddr + ql * (SCREEN_M * 8) + 8u * (uint32_t)(lane & 15);
-                        const uint32_t ta = tbase + 4u * ql;
-                        uint2 v2;
-                        float wt, ws, em, k1, k2;
-                        asm volatile("ds_read_b64 %0, %6\n\t"
-                                     "ds_read_b32 %1, %7\n\t"
-                                     "ds_read_b32 %2, %7 offset:512\n\t"
-                                     "ds_read_b32 %3, %7 offset:2048\n\t"
-                                     "ds_read_b32 %4, %7 offset:1024\n\t"
-                                     "ds_read_b32 %5, %7 offset:1536\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=v"(v2), "=v"(wt), "=v"(ws), "=v"(em), "=v"(k1), "=v"(k2)
-                                     : "v"(la), "v"(ta)
-                                     : "memory");
-                        uint64_t v = ((uint64_t)v2.y << 32) | v2.x;
-                        const int li = lane & 15;
-#pragma unroll
-                        for (int nr = 0; nr < 16; nr++) {
-                            const uint64_t m64 = ((vm[nr >> 2] >> (16 * (nr & 3))) & 0xFFFFull) * 0x0001000100010001ull;
-                            float nrm;  // the row norm of this lane's column (read here: 16 fewer live VGPRs)
-                            asm volatile("ds_read_b32 %0, %1 offset:%2\n\t"
-                                         "s_waitcnt lgkmcnt(0)"
-                                         : "=v"(nrm)
-                                         : "v"(nbase + nsoff), "n"(64 * nr)
-                                         : "memory");
-                            const float u = agpr_read(acc[nr][gi]) + __builtin_fmaf(nrm, k1, k2);
-                            uint64_t pass = __ballot(!(u < ws)) & m64;
-                            while (pass) {
-                                const int j = __builtin_ctzll(pass);
-                                pass &= pass - 1;
-                                const int g = j >> 4;
-                                const float lower =
-                                    sc_lower(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j)), cosine);
-                                float wtg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wt), j));
-                                if (!(lower <= wtg)) continue;
-                                const uint64_t key = ((uint64_t)wvg_ord_f32(lower) << 32) |
-                                                     (uint32_t)(slot0 + 16u * (uint32_t)nr + (uint32_t)(j & 15));
-                                if (!(key < readlane64(v, 16 * g + SCREEN_M - 1))) continue;
-                                const bool inrow = (lane >> 4) == g;
-                                const int pos = __popcll(__ballot(inrow && v < key));
-                                const uint64_t sh = row_shr1_64(v);
-                                v = inrow ? (li > pos ? sh : (li == pos ? key : v)) : v;
-                                const uint64_t nk = readlane64(v, 16 * g + K - 1);
-                                const uint64_t nm = readlane64(v, 16 * g + SCREEN_M - 1);
-                                const float emg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(em), j));
-                                if (nk != WVG_KEY_NONE) wtg = fminf(wtg, sc_tau_k(key_lower(nk), emg, cosine));
-                                if (nm != WVG_KEY_NONE) wtg = fminf(wtg, key_lower(nm));
-                                const float wsg = sc_sigma(wtg, cosine);
-                                wt = inrow ? wtg : wt;
-                                ws = inrow ? wsg : ws;
-                                pass &= ~(0xFFFFull << (16 * g)) | __ballot(!(u < ws));
-                            }
-                        }
-                        const uint2 o2 = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-                        asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(o2) : "memory");
-                        if (li == 0)
-                            asm volatile("ds_write_b32 %0, %1\n\t"
-                                         "ds_write_b32 %0, %2 offset:512" ::"v"(ta), "v"(wt), "v"(ws)
-                                         : "memory");
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    });
-                }
-            } else if constexpr ((DIAG & 8) != 0) {
-                // diagnostic (DIAG 10): the stage loop alone, the accumulators consumed by one sum
-                float x = 0.f;
-#pragma unroll
-                for (int nr = 0; nr < 16; nr++) x += agpr_read(acc[nr][0]);
-                if (x == 0x1p-120f) a.partials[0] = 0;
-            }
-#pragma unroll
-            for (int nr = 0; nr < 16; nr++) acc[nr] = (floatx4){0.f, 0.f, 0.f, 0.f};
-            read_q(I0{}, I0{}, bq0, rbase);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int ql = 0; ql < 16; ql++) {
-        const uint32_t q = q0 + (uint32_t)(16 * w + ql);
-        if (q >= a.nq) break;
-        const uint64_t x = lane < M ? lists[((size_t)w * 16 + ql) * M + lane] : WVG_KEY_NONE;
-        uint64_t *out = a.partials + ((size_t)q * a.nrr + rr) * M;
-        if (lane < M) out[lane] = x;
-        if (lane == K - 1 && x != WVG_KEY_NONE) {
-            const float t = sc_tau_k(key_lower(x), cem[16 * w + ql], cosine);
-            atomicMin(a.gbound + q, wvg_ord_f32(t));
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// K3g (round 5, tools variant 4): K3f's 16-query waves in 4-wave workgroups of
-// 64 queries, TWO workgroups per CU, each with its own 4-stage ring and its
-// own barrier.  K3f's 8 waves shared one barrier per unit, so the two waves of
-// a SIMD issued MFMAs, DMA and reads in the same phase; two independent
-// workgroups drift apart, so one wave's DMA issue and barrier wait can fall in
-// the other's MFMA stream.  Costs: every CU streams each row block twice (once
-// per 64-query workgroup; L2 hits) and the ring holds 2 stages in flight
-// instead of 6.
-constexpr int SG_WAVES = 4;
-constexpr int SG_BQ = 64;
-constexpr int SG_NBUF = 4;
-constexpr int SG_RING = SG_NBUF * SD_STAGE + 2 * SD_NSLOT;
-constexpr int SG_LISTS = SG_BQ * SCREEN_M * 8;
-constexpr int SG_LDS = SG_RING + SG_LISTS + SG_BQ * 4 * 5;
-static_assert(2 * SG_LDS <= 160 * 1024, "K3g: two workgroups per CU");
-static_assert(SG_WAVES * 16 == SG_BQ, "K3g: 16 queries per wave");
-
-template <int KBN, int DIAG = 0>
-__global__ __launch_bounds__(SG_WAVES * 64, 2) void screen_ar16x2_kernel(ScreenArgs a)
-{
-    static_assert(KBN % SG_NBUF == 0, "the stage buffer of a K block must be a compile-time constant");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + SG_RING);  // [4][16][M]
-    float *tau = reinterpret_cast<float *>(smem + SG_RING + SG_LISTS);
-    float *sig = tau + SG_BQ;
-    float *ck1 = sig + SG_BQ;
-    float *ck2 = ck1 + SG_BQ;
-    float *cem = ck2 + SG_BQ;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int K = (int)a.k, M = SCREEN_M;
-    const int cosine = a.cosine;
-    const uint32_t b = blockIdx.x;
-    uint32_t qb, rr;
-    if (a.nrr_l % 8 == 0) {
-        const uint32_t xcd = b % 8, wv = b / 8;
-        qb = wv % a.nqb;
-        rr = a.rr0 + (wv / a.nqb) * 8 + xcd;
-    } else {
-        qb = b % a.nqb;
-        rr = a.rr0 + b / a.nqb;
-    }
-    const uint64_t ntiles = a.tile_end - a.tile_begin;
-    const uint64_t nblk = (ntiles + 3) / 4;
-    const uint64_t blk0 = nblk * rr / a.nrr, blk1 = nblk * (rr + 1) / a.nrr;
-    const uint32_t q0 = qb * SG_BQ;
-
-    for (int i = tid; i < SG_BQ; i += SG_WAVES * 64) {
-        const uint32_t q = q0 + (uint32_t)i;
-        ck1[i] = a.k1[q];
-        ck2[i] = a.k2[q];
-        cem[i] = a.emax[q];
-        const uint32_t g = q < a.nq ? __hip_atomic_load(a.gbound + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        const float t = q >= a.nq ? -__builtin_inff() : (g == 0xFFFFFFFFu ? __builtin_inff() : wvg_unord_f32(g));
-        tau[i] = t;
-        sig[i] = q >= a.nq ? __builtin_inff() : sc_sigma(t, cosine);
-    }
-    for (int i = tid; i < SG_BQ * M; i += SG_WAVES * 64) lists[i] = WVG_KEY_NONE;
-    __syncthreads();
-    const uint32_t laddr = (uint32_t)(uintptr_t)(lists + (size_t)w * 16 * M);
-    const uint32_t tbase = (uint32_t)(uintptr_t)(tau + w * 16);  // sig + 256, ck1 + 512, ck2 + 768, cem + 1024
-    if (blk0 < blk1) {
-        // the wave's 16 queries, every K block, resident for the whole range: the
-        // compiler splits a 256-register wave's file 128 / 128 between VGPRs and
-        // AGPRs, so the first SF_AKB K blocks sit next to the accumulators (64) and
-        // the quarter buffers (32) in AGPRs, the rest in VGPRs
-        constexpr int SF_AKB = 8;
-        bf16x8 areg[KBN];
-        {
-            const uint4 *qsrc = a.qfrag + (size_t)(qb * 4 + w) * KBN * 64 + lane;
-#pragma unroll
-            for (int ks = 0; ks < KBN; ks++) {
-                if (ks < SF_AKB)
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(areg[ks]) : "v"(qsrc + (size_t)ks * 64) : "memory");
-                else
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(areg[ks]) : "v"(qsrc + (size_t)ks * 64) : "memory");
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int ks = 0; ks < KBN; ks++) {
-                if (ks < SF_AKB)
-                    asm volatile("" : "+a"(areg[ks]));
-                else
-                    asm volatile("" : "+v"(areg[ks]));
-            }
-        }
-        // loads of one stage (K3d's): wave w moves row fragments 4 w .. 4 w + 3 (tile w),
-        // with unit 0 also the norms of tile w, and wave 0 the block's tile words
-        const uint4 *lsrc = a.shadow + ((size_t)(a.tile_begin + blk0 * 4 + w) * KBN * 4) * 64;
-        const float *lnorm = a.norms + (a.tile_begin + blk0 * 4 + w) * 64;
-        uint64_t lblk = blk0;
-        auto load_stage = [&](int ks) {
-            unsigned char *dst = smem + (ks % SG_NBUF) * SD_STAGE;
-#pragma unroll
-            for (int rg = 0; rg < 4; rg++)
-                __builtin_amdgcn_global_load_lds(lsrc + ((size_t)ks * 4 + rg) * 64 + lane,
-                                                 reinterpret_cast<uint4 *>(dst + (4 * w + rg) * 1024), 16, 0, 0);
-            unsigned char *nslot = smem + SG_NBUF * SD_STAGE + (lblk & 1) * SD_NSLOT;
-            if (ks == 0)
-                __builtin_amdgcn_global_load_lds(lnorm + lane, reinterpret_cast<float *>(nslot + w * 256), 4, 0, 0);
-            if (ks == 0 && w == 0) {
-                const uint32_t wi = (uint32_t)(lane & 7) >> 1, half = lane & 1;
-                const uint64_t t = a.tile_begin + lblk * 4 + wi;
-                const uint32_t *src =
-                    reinterpret_cast<const uint32_t *>(a.valid + (t < a.tile_end ? t : a.tile_end - 1)) + half;
-                if (lane >= 8 && lane < 16 && a.allow) {
-                    const uint64_t aw = t - a.allow_t0;
-                    src = reinterpret_cast<const uint32_t *>(a.allow + (aw < a.allow_words ? aw : 0)) + half;
-                }
-                __builtin_amdgcn_global_load_lds(src, reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
-            }
-            if (ks == KBN - 1 && lblk + 1 < blk1) {  // the load cursor moves on; past the end it stays
-                ++lblk;
-                lsrc += (size_t)4 * KBN * 4 * 64;
-                lnorm += 256;
-            }
-        };
-        // SG_NBUF - 2 stages in flight at every wait: unit ks + 1 landed, the loads of
-        // units ks + 2 .. ks + SG_NBUF - 2 left outstanding (K3d's per-unit load counts)
-        auto wait_next = [&](auto KS) {
-            constexpr int ks = decltype(KS)::value;
-            constexpr int n0 = sd_younger<KBN, 0>(ks + 1, SG_NBUF - 3, true);
-            constexpr int n1 = sd_younger<KBN, 0>(ks + 1, SG_NBUF - 3, false);
-            if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n0) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n1) : "memory");
-        };
-        auto raw_barrier = [&]() {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        };
-        // A quarter stage (row fragments 4 qq .. 4 qq + 3) straight into AGPRs, in
-        // flight while the previous quarter's MFMAs issue; consumers pass wait_q
-        // (lgkmcnt(4): every read but the 4 younger ones landed) or the barrier.
-        // The stage / quarter offset is an instruction literal (as SGPR operands the
-        // 32 distinct offsets were hoisted into SGPRs and spilled).
-        const uint32_t rbase = (uint32_t)(uintptr_t)smem + 16u * lane;
-        auto read_q = [](auto KS, auto QQ, bf16x8 (&br)[4], uint32_t rb) {
-            constexpr uint32_t soff =
-                (uint32_t)((decltype(KS)::value % SG_NBUF) * SD_STAGE + decltype(QQ)::value * 4 * 1024);
-            uint32_t tmp;
-            asm volatile("v_add_u32 %4, %5, %6\n\t"
-                         "ds_read_b128 %0, %4\n\t"
-                         "ds_read_b128 %1, %4 offset:1024\n\t"
-                         "ds_read_b128 %2, %4 offset:2048\n\t"
-                         "ds_read_b128 %3, %4 offset:3072"
-                         : "=a"(br[0]), "=a"(br[1]), "=a"(br[2]), "=a"(br[3]), "=&v"(tmp)
-                         : "n"(soff), "v"(rb)
-                         : "memory");
-        };
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
-        using I3 = std::integral_constant<int, 3>;
-        auto wait_q = [&](bf16x8 (&br)[4]) {
-            asm volatile("s_waitcnt lgkmcnt(4)" : "+a"(br[0]), "+a"(br[1]), "+a"(br[2]), "+a"(br[3]) : : "memory");
-        };
-        const int qlane = 4 * (lane >> 4);
-        const uint32_t sbase = (uint32_t)(uintptr_t)smem;
-        const uint32_t nbase = sbase + 4u * (uint32_t)(lane & 15);
-        const uint32_t qbase = sbase + 4u * (uint32_t)qlane;
-        const uint32_t csoff = (uint32_t)((uintptr_t)sig - (uintptr_t)smem);
-        bool lane_force = false;
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            if (!(ck1[16 * w + qlane + r] <= 0x1p50f)) lane_force = true;
-
-        floatx4 acc[16];
-#pragma unroll
-        for (int nr = 0; nr < 16; nr++) acc[nr] = (floatx4){0.f, 0.f, 0.f, 0.f};
-        bf16x8 bq0[4], bq1[4];
-        auto mfma4 = [&](int ks, int qq, bf16x8 (&br)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                acc[4 * qq + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(areg[ks], br[j], acc[4 * qq + j], 0, 0, 0);
-        };
-#pragma unroll
-        for (int ks = 0; ks < SG_NBUF - 1; ks++) load_stage(ks);
-        if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, 0>(0, SG_NBUF - 2, true)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, 0>(0, SG_NBUF - 2, false)) : "memory");
-        raw_barrier();
-        read_q(I0{}, I0{}, bq0, rbase);
-        for (uint64_t blk = blk0; blk < blk1; blk++) {
-            sd_static_for<KBN>([&](auto KS) {
-                constexpr int ks = decltype(KS)::value;
-                read_q(KS, I1{}, bq1, rbase);
-                wait_q(bq0);
-                mfma4(ks, 0, bq0);
-                read_q(KS, I2{}, bq0, rbase);
-                wait_q(bq1);
-                mfma4(ks, 1, bq1);
-                read_q(KS, I3{}, bq1, rbase);
-                wait_q(bq0);
-                mfma4(ks, 2, bq0);
-                wait_next(KS);  // the next unit landed
-                raw_barrier();  // (lgkmcnt(0): quarter 3 landed)
-#pragma unroll
-                for (int j = 0; j < 4; j++) asm volatile("" : "+a"(bq1[j]));
-                load_stage((ks + SG_NBUF - 1) % KBN);  // into the buffer of unit - 1, read before the barrier
-                if constexpr (ks + 1 < KBN) read_q(std::integral_constant<int, ks + 1>{}, I0{}, bq0, rbase);
-                mfma4(ks, 3, bq1);
-            });
-            // XDL write -> VALU read of the accumulators through agpr_read: see K3d
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr ((DIAG & 2) == 0) {
-                // K3d's epilogue over the wave's 16 queries: C layout row (query) qlane + r,
-                // column (row) 16 nr + (lane & 15); fast check per query r, exact test on
-                // the groups it could not rule out
-                const uint32_t nsoff = (uint32_t)(SG_NBUF * SD_STAGE + (blk & 1) * SD_NSLOT);
-                auto read_norms8 = [&](int hh, float (&nrm)[8]) {
-                    uint32_t tmp;
-                    asm volatile("v_add_u32 %8, %9, %10\n\t"
-                                 "ds_read_b32 %0, %8\n\t"
-                                 "ds_read_b32 %1, %8 offset:64\n\t"
-                                 "ds_read_b32 %2, %8 offset:128\n\t"
-                                 "ds_read_b32 %3, %8 offset:192\n\t"
-                                 "ds_read_b32 %4, %8 offset:256\n\t"
-                                 "ds_read_b32 %5, %8 offset:320\n\t"
-                                 "ds_read_b32 %6, %8 offset:384\n\t"
-                                 "ds_read_b32 %7, %8 offset:448\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=v"(nrm[0]), "=v"(nrm[1]), "=v"(nrm[2]), "=v"(nrm[3]), "=v"(nrm[4]),
-                                   "=v"(nrm[5]), "=v"(nrm[6]), "=v"(nrm[7]), "=&v"(tmp)
-                                 : "s"(nsoff + 512u * hh), "v"(nbase)
-                                 : "memory");
-                };
-                float nmax, nsum;
-                {
-                    float n0[8], n1[8];
-                    read_norms8(0, n0);
-                    read_norms8(1, n1);
-                    nmax = n0[0];
-                    nsum = n0[0];
-#pragma unroll
-                    for (int j2 = 1; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n0[j2]), nsum += n0[j2];
-#pragma unroll
-                    for (int j2 = 0; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n1[j2]), nsum += n1[j2];
-                }
-                const bool force = lane_force || !(nmax <= 0x1p60f) || nsum != nsum;
-                uint32_t wact = 0;
-                {
-                    const uint32_t coff = (uint32_t)(csoff + 4 * (16 * w));
-                    float4 k1v, k2v, sv;
-                    uint32_t tmp;
-                    asm volatile("v_add_u32 %3, %4, %5\n\t"
-                                 "ds_read_b128 %0, %3 offset:256\n\t"
-                                 "ds_read_b128 %1, %3 offset:512\n\t"
-                                 "ds_read_b128 %2, %3\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=v"(k1v), "=v"(k2v), "=v"(sv), "=&v"(tmp)
-                                 : "s"(coff), "v"(qbase)
-                                 : "memory");
-                    const float k1r[4] = {k1v.x, k1v.y, k1v.z, k1v.w};
-                    const float k2r[4] = {k2v.x, k2v.y, k2v.z, k2v.w};
-                    const float svr[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        float m = agpr_read(acc[0][r]);
-#pragma unroll
-                        for (int nr = 1; nr < 16; nr++) m = __builtin_fmaxf(m, agpr_read(acc[nr][r]));
-                        const float t = (m + __builtin_fmaf(nmax, k1r[r], k2r[r])) - svr[r];
-                        if (__ballot(force || t >= 0.f)) wact |= 1u << r;
-                    }
-                }
-                if (wact != 0) {
-                    uint64_t vm[4];
-                    {
-                        uint4 vw0, vw1, aw0, aw1;
-                        uint32_t tmp;
-                        asm volatile("v_add_u32 %4, %5, %6\n\t"
-                                     "ds_read_b128 %0, %4 offset:1024\n\t"
-                                     "ds_read_b128 %1, %4 offset:1040\n\t"
-                                     "ds_read_b128 %2, %4 offset:1056\n\t"
-                                     "ds_read_b128 %3, %4 offset:1072\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=v"(vw0), "=v"(vw1), "=v"(aw0), "=v"(aw1), "=&v"(tmp)
-                                     : "s"(nsoff), "v"(sbase)
-                                     : "memory");
-                        const uint64_t words[4] = {((uint64_t)vw0.y << 32) | vw0.x, ((uint64_t)vw0.w << 32) | vw0.z,
-                                                   ((uint64_t)vw1.y << 32) | vw1.x, ((uint64_t)vw1.w << 32) | vw1.z};
-                        const uint64_t allows[4] = {((uint64_t)aw0.y << 32) | aw0.x, ((uint64_t)aw0.w << 32) | aw0.z,
-                                                    ((uint64_t)aw1.y << 32) | aw1.x, ((uint64_t)aw1.w << 32) | aw1.z};
-#pragma unroll
-                        for (int h = 0; h < 4; h++) {
-                            const uint64_t t = a.tile_begin + blk * 4 + h;
-                            uint64_t m = t < a.tile_end ? readfirstlane64(words[h]) : 0ull;
-                            if (a.allow) {
-                                const uint64_t aw = t - a.allow_t0;
-                                m &= aw < a.allow_words ? readfirstlane64(allows[h]) : 0ull;
-                            }
-                            vm[h] = m;
-                        }
-                    }
-                    const uint64_t slot0 = (a.tile_begin + blk * 4) * 64;
-                    // per active query slot gi: lane l tests its column's 16 rows against query
-                    // qlane + gi, and row l >> 4 of v holds that query's list (K3d's slow path;
-                    // four groups, each its own unrolled copy reading its accumulators in place)
-                    sd_static_for<4>([&](auto G) {
-                        constexpr int gi = decltype(G)::value;
-                        if (((wact >> gi) & 1u) == 0) return;
-                        const uint32_t ql = (uint32_t)gi + (uint32_t)qlane;
-                        const uint32_t la = laddr + ql * (SCREEN_M * 8) + 8u * (uint32_t)(lane & 15);
-                        const uint32_t ta = tbase + 4u * ql;
-                        uint2 v2;
-                        float wt, ws, em, k1, k2;
-                        asm volatile("ds_read_b64 %0, %6\n\t"
-                                     "ds_read_b32 %1, %7\n\t"
-                                     "ds_read_b32 %2, %7 offset:256\n\t"
-                                     "ds_read_b32 %3, %7 offset:1024\n\t"
-                                     "ds_read_b32 %4, %7 offset:512\n\t"
-                                     "ds_read_b32 %5, %7 offset:768\n\t"
-                                     "s_waitcnt lgkmcnt(0)"
-                                     : "=v"(v2), "=v"(wt), "=v"(ws), "=v"(em), "=v"(k1), "=v"(k2)
-                                     : "v"(la), "v"(ta)
-                                     : "memory");
-                        uint64_t v = ((uint64_t)v2.y << 32) | v2.x;
-                        const int li = lane & 15;
-#pragma unroll
-                        for (int nr = 0; nr < 16; nr++) {
-                            const uint64_t m64 = ((vm[nr >> 2] >> (16 * (nr & 3))) & 0xFFFFull) * 0x0001000100010001ull;
-                            float nrm;  // the row norm of this lane's column (read here: 16 fewer live VGPRs)
-                            asm volatile("ds_read_b32 %0, %1 offset:%2\n\t"
-                                         "s_waitcnt lgkmcnt(0)"
-                                         : "=v"(nrm)
-                                         : "v"(nbase + nsoff), "n"(64 * nr)
-                                         : "memory");
-                            const float u = agpr_read(acc[nr][gi]) + __builtin_fmaf(nrm, k1, k2);
-                            uint64_t pass = __ballot(!(u < ws)) & m64;
-                            while (pass) {
-                                const int j = __builtin_ctzll(pass);
-                                pass &= pass - 1;
-                                const int g = j >> 4;
-                                const float lower =
-                                    sc_lower(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j)), cosine);
-                                float wtg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wt), j));
-                                if (!(lower <= wtg)) continue;
-                                const uint64_t key = ((uint64_t)wvg_ord_f32(lower) << 32) |
-                                                     (uint32_t)(slot0 + 16u * (uint32_t)nr + (uint32_t)(j & 15));
-                                if (!(key < readlane64(v, 16 * g + SCREEN_M - 1))) continue;
-                                const bool inrow = (lane >> 4) == g;
-                                const int pos = __popcll(__ballot(inrow && v < key));
-                                const uint64_t sh = row_shr1_64(v);
-                                v = inrow ? (li > pos ? sh : (li == pos ? key : v)) : v;
-                                const uint64_t nk = readlane64(v, 16 * g + K - 1);
-                                const uint64_t nm = readlane64(v, 16 * g + SCREEN_M - 1);
-                                const float emg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(em), j));
-                                if (nk != WVG_KEY_NONE) wtg = fminf(wtg, sc_tau_k(key_lower(nk), emg, cosine));
-                                if (nm != WVG_KEY_NONE) wtg = fminf(wtg, key_lower(nm));
-                                const float wsg = sc_sigma(wtg, cosine);
-                                wt = inrow ? wtg : wt;
-                                ws = inrow ? wsg : ws;
-                                pass &= ~(0xFFFFull << (16 * g)) | __ballot(!(u < ws));
-                            }
-                        }
-                        const uint2 o2 = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-                        asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(o2) : "memory");
-                        if (li == 0)
-                            asm volatile("ds_write_b32 %0, %1\n\t"
-                                         "ds_write_b32 %0, %2 offset:256" ::"v"(ta), "v"(wt), "v"(ws)
-                                         : "memory");
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    });
-                }
-            } else if constexpr ((DIAG & 8) != 0) {
-                // diagnostic (DIAG 10): the stage loop alone, the accumulators consumed by one sum
-                float x = 0.f;
-#pragma unroll
-                for (int nr = 0; nr < 16; nr++) x += agpr_read(acc[nr][0]);
-                if (x == 0x1p-120f) a.partials[0] = 0;
-            }
-#pragma unroll
-            for (int nr = 0; nr < 16; nr++) acc[nr] = (floatx4){0.f, 0.f, 0.f, 0.f};
-            read_q(I0{}, I0{}, bq0, rbase);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int ql = 0; ql < 16; ql++) {
-        const uint32_t q = q0 + (uint32_t)(16 * w + ql);
-        if (q >= a.nq) break;
-        const uint64_t x = lane < M ? lists[((size_t)w * 16 + ql) * M + lane] : WVG_KEY_NONE;
-        uint64_t *out = a.partials + ((size_t)q * a.nrr + rr) * M;
-        if (lane < M) out[lane] = x;
-        if (lane == K - 1 && x != WVG_KEY_NONE) {
-            const float t = sc_tau_k(key_lower(x), cem[16 * w + ql], cosine);
-            atomicMin(a.gbound + q, wvg_ord_f32(t));
-        }
-    }
-}
-
-#endif  // WVG_TOOLS
 
 // ---------------------------------------------------------------------------
 // Collect, per query.  Every range list holds its range's SCREEN_M smallest
@@ -3544,14 +2259,77 @@ uint32_t screen_row_ranges(uint32_t nq, uint64_t ntiles, int num_cus)
     return (uint32_t)want;
 }
 
+// The screen kernels: every compiled instantiation with its launch geometry.
+// K3c takes any K-block count (kbn 0 here); the register-resident layouts
+// exist per count.
+enum ScreenLayout { SL_K3C, SL_1X4, SL_2X2 };  // K3c; K3d / K3i, 1 x 4 waves; K3i, 2 x 2 waves
+struct ScreenKernel {
+    bool i8;
+    uint32_t kbn;
+    ScreenLayout layout;
+    int diag;
+    void (*fn)(ScreenArgs);
+    uint32_t lds, threads;  // dynamic LDS bytes, workgroup size
+};
+static const ScreenKernel SCREEN_KERNELS[] = {
+    {false, 0, SL_K3C, 0, &screen_kernel, SC_LDS, SC_WAVES * 64},
+    {false, 16, SL_1X4, 0, &screen_ar_kernel<16>, SD_LDS, SD_WAVES * 64},
+    {false, 24, SL_1X4, 0, &screen_ar_kernel<24>, SD_LDS, SD_WAVES * 64},
+    {true, 8, SL_1X4, 0, &screen_ar_kernel<8, 0, true>, si_lds(si_nbuf(8)), SD_WAVES * 64},
+    {true, 12, SL_1X4, 0, &screen_ar_kernel<12, 0, true>, si_lds(si_nbuf(12)), SD_WAVES * 64},
+    {true, 16, SL_1X4, 0, &screen_ar_kernel<16, 0, true>, si_lds(si_nbuf(16)), SD_WAVES * 64},
+    {true, 8, SL_2X2, 0, &screen_i8_kernel<8>, SJ_LDS, SD_WAVES * 64},
+    {true, 12, SL_2X2, 0, &screen_i8_kernel<12>, SJ_LDS, SD_WAVES * 64},
+#ifdef WVG_TOOLS  // Tuning::screen_diag: 4 = no exact path, 10 = the stage loop alone, 16 = counters
+    {false, 24, SL_1X4, 4, &screen_ar_kernel<24, 4>, SD_LDS, SD_WAVES * 64},
+    {false, 24, SL_1X4, 10, &screen_ar_kernel<24, 10>, SD_LDS, SD_WAVES * 64},
+    {false, 24, SL_1X4, 16, &screen_ar_kernel<24, 16>, SD_LDS, SD_WAVES * 64},
+    {true, 12, SL_1X4, 10, &screen_ar_kernel<12, 10, true>, si_lds(si_nbuf(12)), SD_WAVES * 64},
+    {true, 12, SL_2X2, 4, &screen_i8_kernel<12, 4>, SJ_LDS, SD_WAVES * 64},
+    {true, 12, SL_2X2, 10, &screen_i8_kernel<12, 10>, SJ_LDS, SD_WAVES * 64},
+    {true, 12, SL_2X2, 16, &screen_i8_kernel<12, 16>, SJ_LDS, SD_WAVES * 64},
+#endif
+};
+
+// The kernel of a launch: K3i on an int8 shadow -- 2 x 2 waves for d = 512 /
+// 768, K3d's 1 x 4 layout for d = 1024 (64 resident queries would not fit the
+// registers) or on request (variant 5); else K3d where its template applies
+// (and variant is not 1), else K3c.  nullptr: no such kernel (a variant or
+// diagnostic that this build or this (int8, kbn) does not have).
+static const ScreenKernel *pick_screen_kernel(bool i8, uint32_t kbn, int variant, int diag)
+{
+    // every kernel's dynamic-LDS limit, once
+    static const bool attr = [] {
+        bool ok = true;
+        for (const ScreenKernel &k : SCREEN_KERNELS)
+            ok &= hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)k.lds) == hipSuccess;
+        return ok;
+    }();
+    (void)attr;
+    if (variant != 0 && variant != (i8 ? 5 : 1)) return nullptr;
+    ScreenLayout layout;
+    if (i8)
+        layout = variant == 5 || kbn > 12 ? SL_1X4 : SL_2X2;
+    else
+        layout = variant == 1 || (kbn != 16 && kbn != 24) ? SL_K3C : SL_1X4;
+    if (layout == SL_K3C) kbn = 0;
+    for (const ScreenKernel &k : SCREEN_KERNELS)
+        if (k.i8 == i8 && k.kbn == kbn && k.layout == layout && k.diag == diag) return &k;
+    return nullptr;
+}
+
 hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
 {
     const bool i8 = L.i8 && screen_i8_supported(L.dim);
     const uint32_t kbn = i8 ? L.dim / 64 : screen_kblocks(L.dim);  // (K3i: 64-deep int8 K blocks)
-    const uint32_t nq16 = (L.nq + 15) / 16, nq_pad = (L.nq + SC_BQ - 1) / SC_BQ * SC_BQ;
-    uint32_t nqb = nq_pad / SC_BQ;  // (K3g, tools: 64-query blocks)
+    const uint32_t nq_pad = (L.nq + SC_BQ - 1) / SC_BQ * SC_BQ, nqb = nq_pad / SC_BQ;
     hipError_t e;
-    (void)nq16;
+    // the kernel first: an unsupported (variant, diag) starts nothing
+    const ScreenKernel *sk = pick_screen_kernel(i8, kbn, tuning().screen_variant, tuning().screen_diag);
+    if (!sk) return hipErrorInvalidValue;
+    void (*const kern)(ScreenArgs) = sk->fn;
+    const uint32_t lds = sk->lds, threads = sk->threads;
     if (i8) {
         // K3i: per-query scale and bound constants first, then the int8 fragments at that scale
         hipLaunchKernelGGL(screen_qconst_i8_kernel, dim3(nq_pad / 4), dim3(256), 0, s, L.queries, L.nq, L.qpitch,
@@ -3654,113 +2432,11 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
     a.nqb = nqb;
     a.nrr = L.nrr;
     a.cosine = L.cosine;
-#ifdef WVG_TOOLS
-    a.diag = tuning().screen_diag;
-#endif
     a.gbound = L.gbound;
     a.partials = L.partials;
     a.errs = L.errs;
     a.kb = L.kb;
     a.css = L.css;
-    static bool attr = [] {
-        return hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS) == hipSuccess &&
-               hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_ar_kernel<16>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SD_LDS) == hipSuccess &&
-               hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_ar_kernel<24>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SD_LDS) == hipSuccess &&
-               hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_ar_kernel<8, 0, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, si_lds(si_nbuf(8))) == hipSuccess &&
-               hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_ar_kernel<12, 0, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, si_lds(si_nbuf(12))) == hipSuccess &&
-               hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_ar_kernel<16, 0, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, si_lds(si_nbuf(16))) == hipSuccess &&
-               hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_i8_kernel<8>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SJ_LDS) == hipSuccess &&
-               hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_i8_kernel<12>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SJ_LDS) == hipSuccess;
-    }();
-    (void)attr;
-    // K3i on an int8 shadow; else K3d (queries resident in registers) where its template applies, else K3c
-    void (*kern)(ScreenArgs) = kbn == 24 ? &screen_ar_kernel<24> : kbn == 16 ? &screen_ar_kernel<16> : nullptr;
-    // (d = 512 / 768: the 2 x 2-wave layout; d = 1024: 64 resident queries would not fit the
-    // registers, K3d's layout)
-    bool i8_22 = i8 && kbn <= 12;
-#ifdef WVG_TOOLS
-    if (tuning().screen_variant == 5) i8_22 = false;  // A/B: K3i on K3d's 1 x 4 layout
-#endif
-    if (i8)
-        kern = i8_22 ? (kbn == 8 ? &screen_i8_kernel<8> : &screen_i8_kernel<12>)
-                     : (kbn == 8 ? &screen_ar_kernel<8, 0, true>
-                                 : (kbn == 12 ? &screen_ar_kernel<12, 0, true> : &screen_ar_kernel<16, 0, true>));
-#ifdef WVG_TOOLS
-    if (i8_22 && kbn == 12 && (tuning().screen_diag == 4 || tuning().screen_diag == 10 || tuning().screen_diag == 16)) {
-        kern = tuning().screen_diag == 4    ? &screen_i8_kernel<12, 4>
-               : tuning().screen_diag == 10 ? &screen_i8_kernel<12, 10>
-                                            : &screen_i8_kernel<12, 16>;  // K3i diagnostics
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  SJ_LDS);
-    }
-#endif
-    bool k3f = false;
-#ifdef WVG_TOOLS
-    bool k3g = false;
-    if (i8 && tuning().screen_diag == 10 && kbn == 12) {  // K3i's stage loop alone (A/B)
-        kern = &screen_ar_kernel<12, 10, true>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  si_lds(si_nbuf(12)));
-    }
-    if (!i8) {
-    if (tuning().screen_variant == 2 && kern)  // K3e (32x32x16 MFMAs)
-        kern = kbn == 24 ? &screen_ar32_kernel<24> : &screen_ar32_kernel<16>;
-    if (tuning().screen_variant == 3 && kern)  // K3f (two waves per SIMD)
-        kern = kbn == 24 ? &screen_ar16_kernel<24> : &screen_ar16_kernel<16>;
-    k3g = tuning().screen_variant == 4 && kern;  // K3g (two 4-wave workgroups per CU)
-    if (k3g) kern = kbn == 24 ? &screen_ar16x2_kernel<24> : &screen_ar16x2_kernel<16>;
-    if (tuning().screen_variant >= 2 && kern)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  k3g ? SG_LDS : SD_LDS);
-    if (kbn == 24) {  // K3d diagnostics: separately compiled instantiations
-        switch (tuning().screen_diag) {
-        case 1: kern = &screen_ar_kernel<24, 1>; break;
-        case 2: kern = &screen_ar_kernel<24, 2>; break;
-        case 4: kern = &screen_ar_kernel<24, 4>; break;
-        case 16: kern = &screen_ar_kernel<24, 16>; break;
-        case 10: kern = &screen_ar_kernel<24, 10>; break;
-        case 42: kern = &screen_ar_kernel<24, 42>; break;    // 10 without the norm / tile-word loads
-        case 106: kern = &screen_ar_kernel<24, 106>; break;  // 42 without the per-unit s_barrier
-        case 138: kern = &screen_ar_kernel<24, 138>; break;  // 10 without any stage load
-        case 202: kern = &screen_ar_kernel<24, 202>; break;  // 138 without the s_barrier
-        case 32: kern = &screen_ar_kernel<24, 32>; break;    // the product without the norm / tile-word loads
-        case 256: kern = &screen_ar_kernel<24, 256>; break;  // round 3's norms / words with every unit
-        case 266: kern = &screen_ar_kernel<24, 266>; break;  // 10 with round 3's per-unit norms / words
-        case 1024: kern = &screen_ar_kernel<24, 1024>; break;  // one barrier per two K blocks
-        case 2048: kern = &screen_ar_kernel<24, 2048>; break;  // the per-element (tight) fast check
-        case 2064: kern = &screen_ar_kernel<24, 2064>; break;  // 2048 with the counters (16)
-        case 1034: kern = &screen_ar_kernel<24, 1034>; break;  // 10 with one barrier per two K blocks
-        default: break;
-        }
-        if (tuning().screen_variant == 2 && tuning().screen_diag == 10) kern = &screen_ar32_kernel<24, 10>;
-        if (tuning().screen_variant == 3 && tuning().screen_diag == 10) kern = &screen_ar16_kernel<24, 10>;
-        if (kern != &screen_ar_kernel<24> && kern != &screen_ar32_kernel<24> && kern != &screen_ar16_kernel<24>)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      SD_LDS);
-    }
-    if (tuning().screen_variant == 1) kern = nullptr;
-    k3f = kern == &screen_ar16_kernel<24> || kern == &screen_ar16_kernel<16> || kern == &screen_ar16_kernel<24, 10>;
-    }  // (!i8)
-#endif
-#ifdef WVG_TOOLS
-    if (k3g) {  // 64-query workgroups: twice the query blocks
-        nqb = nq_pad / SG_BQ;
-        a.nqb = nqb;
-    }
-    const uint32_t lds = i8_22 ? SJ_LDS : i8 ? si_lds(si_nbuf(kbn)) : k3g ? SG_LDS : kern ? SD_LDS : SC_LDS;
-#else
-    const uint32_t lds = i8_22 ? SJ_LDS : i8 ? si_lds(si_nbuf(kbn)) : kern ? SD_LDS : SC_LDS;
-#endif
-    const uint32_t threads = k3f ? SF_WAVES * 64 : kern ? SD_WAVES * 64 : SC_WAVES * 64;
-    if (!kern) kern = &screen_kernel;
     // Phased screen: the first r1 ranges (one workgroup per CU) run alone; their
     // lists' joint tau* (k-th smallest lower bound over ~10 % of the rows,
     // + 2 Emax) seeds the next phase's thresholds, the next r2 - r1 ranges

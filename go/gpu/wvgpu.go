@@ -963,6 +963,73 @@ func (x *Corpus) SearchDevicePipelined(b DeviceBuffers, nq, k int) error {
 		b.Stream))
 }
 
+// DeviceAllow is a window of per-query allow lists in HBM for
+// SearchDevicePipelinedFiltered: Words holds [nq][Stride] uint64 and bit b of
+// word w of query q's row stands for docID FirstID + 64*w + b; docIDs outside
+// the window are not allowed.  Words == nil means no filter.
+type DeviceAllow struct {
+	Words   unsafe.Pointer // uint64 [nq][Stride], from Ctx.DeviceAlloc
+	Bytes   uint64         // size of the allocation behind Words
+	Stride  uint64         // words per query; 0 = nothing allowed
+	FirstID uint64         // docID of bit 0 of word 0, a multiple of 64
+}
+
+// AllowWindow lays out one AllowList per query as the host image of
+// DeviceAllow.Words ([len(allows)][stride] words, copied with
+// Ctx.CopyWordsToDevice): a nil list allows every docID of the window, an empty
+// one none, and ids outside [firstID, firstID + 64*stride) are dropped.
+func AllowWindow(allows []helpers.AllowList, firstID, stride uint64) ([]uint64, error) {
+	if firstID%64 != 0 {
+		return nil, errors.New("wvgpu: allow window must begin at a multiple of 64")
+	}
+	words := make([]uint64, uint64(len(allows))*stride)
+	for q, allow := range allows {
+		row := words[uint64(q)*stride : uint64(q+1)*stride]
+		if allow == nil {
+			for i := range row {
+				row[i] = ^uint64(0)
+			}
+			continue
+		}
+		it := allow.Iterator()
+		for id, more := it.Next(); more; id, more = it.Next() {
+			if id >= firstID && (id-firstID)/64 < stride {
+				row[(id-firstID)/64] |= 1 << ((id - firstID) % 64)
+			}
+		}
+	}
+	return words, nil
+}
+
+// CopyWordsToDevice copies 64-bit words (an AllowWindow) to HBM on stream s; it
+// returns when the copy is done.
+func (c *Ctx) CopyWordsToDevice(dst unsafe.Pointer, src []uint64, s unsafe.Pointer) error {
+	defer pin(c)()
+	return err(C.wvg_memcpy_h2d(c.h, dst, unsafe.Pointer(u64p(src)), C.uint64_t(8*len(src)), s))
+}
+
+// SearchDevicePipelinedFiltered: SearchDevicePipelined with one allow list per
+// query (a `where` filter's AllowList, V/flat/index.go:423-449), read on the
+// device: per query the results of Search with that list.
+func (x *Corpus) SearchDevicePipelinedFiltered(b DeviceBuffers, nq, k int, allow DeviceAllow) error {
+	defer pin(x)()
+	if nq < 0 || k < 0 {
+		return errors.New("wvgpu: negative nq or k")
+	}
+	if allow.Words != nil {
+		if allow.FirstID%64 != 0 {
+			return errors.New("wvgpu: allow window must begin at a multiple of 64")
+		}
+		if allow.Stride > 0 && (allow.Bytes/8/allow.Stride < uint64(nq)) {
+			return fmt.Errorf("wvgpu: allow window of %d bytes holds fewer than %d rows of %d words", allow.Bytes, nq,
+				allow.Stride)
+		}
+	}
+	return err(C.wvg_search_device_pipelined_filtered(x.h, (*C.float)(b.Queries), C.uint32_t(nq), C.uint32_t(k),
+		(*C.uint64_t)(allow.Words), C.uint64_t(allow.Stride), C.uint64_t(allow.FirstID), (*C.uint64_t)(b.IDs),
+		(*C.float)(b.Dists), (*C.uint32_t)(b.Counts), b.Workspace, C.size_t(b.WsBytes), b.Stream))
+}
+
 // CheckDevice surfaces a device-side failure of earlier device searches.
 func (c *Ctx) CheckDevice(workspace, stream unsafe.Pointer) error {
 	defer pin(c)()

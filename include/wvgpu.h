@@ -351,6 +351,36 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
 int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                                 uint64_t *d_ids, float *d_dists, uint32_t *d_counts,
                                 void *d_workspace, size_t workspace_bytes, void *stream);
+/* wvg_search_device_pipelined with one allow list per query (Weaviate attaches
+ * an AllowList to every query that has a `where` filter; the flat index then
+ * scans only the allowed docIDs, V/flat/index.go:423-449).  The lists are a
+ * window of the docID space, resident on the device: d_allow holds
+ * [nq][allow_stride] 64-bit words and bit b of word w of query q's row stands
+ * for docID allow_first_id + 64 w + b.  allow_first_id must be a multiple of
+ * 64 (WVG_ERR_INVALID otherwise, nothing launched).  Every docID outside
+ * [allow_first_id, allow_first_id + 64 allow_stride) is not allowed; the
+ * window may begin before the corpus's id_base or end after its rows, and bits
+ * that name no row are ignored.  The caller fixes the window because the host
+ * never reads the bitmap (that would need a synchronization); the kernels read
+ * it in place, no copy of it is made in the workspace.
+ * The outputs are exactly what nq calls wvg_search(c, q_i, 1, k, allow_i, ...)
+ * write: ids, distance bits, counts and padding.  allow_stride == 0 or a row
+ * of zeros gives that query an empty result (ids UINT64_MAX, dists +inf,
+ * count 0), as an empty allow list does in wvg_search.  d_allow == NULL is
+ * wvg_search_device_pipelined exactly.  Where the shared-row kernel applies
+ * (see above) the filtered queries share each row read like unfiltered ones:
+ * a query scores only the rows its list allows, and a 64-row tile that no
+ * query of the pass allows is skipped before it is read.  Everywhere else
+ * (one query, other metrics or dims, cache_reuse = 0) every query is one scan
+ * with its own window, followed by a merge launch for nq >= 2.  Otherwise as
+ * wvg_search_device_pipelined: F32 corpora, asynchronous on `stream`, no
+ * allocation, no host synchronization, capturable; the same workspace rule
+ * (wvg_search_workspace_size is unchanged).                                 */
+int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
+                                         const uint64_t *d_allow, uint64_t allow_stride,
+                                         uint64_t allow_first_id, uint64_t *d_ids, float *d_dists,
+                                         uint32_t *d_counts, void *d_workspace, size_t workspace_bytes,
+                                         void *stream);
 /* Synchronizes `stream` and reads (and clears) the workspace's sticky status
  * word: WVG_ERR_DEVICE if any device search on this workspace since the last
  * check could not complete -- the query-stream merge workgroup of

@@ -96,6 +96,9 @@ SIGNATURES = {
                                   c_void_p, c_size_t, c_void_p]),
     "wvg_search_device_pipelined": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_size_t, c_void_p]),
+    "wvg_search_device_pipelined_filtered": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint64,
+                                                     c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                     c_void_p]),
     "wvg_topk_merge_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "wvg_search_device_check": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -329,7 +329,8 @@ struct StreamJob {
 };
 hipError_t launch_scan_f32_stream(const ScanArgs &a, const StreamJob &j, hipStream_t s);
 // Shared-row query stream (scan_f32_qshare_kernel): L2 / dot / cosine F32 corpora
-// of d = 128 or 768 in the AVX2 order, nq >= 2, no allow list.  One launch of
+// of d = 128 or 768 in the AVX2 order, nq >= 2, with or without per-query allow
+// lists (QShareFilt below).  One launch of
 // `groups` scan workgroups + `mergers` merge workgroups.  The queries are taken
 // qshare_queries_per_pass() at a time; a pass walks the wave's tiles once
 // (direction (reverse + pass) & 1) and scores every query of the pass against each
@@ -382,6 +383,23 @@ struct QShareArgs {
                              // half) and all (query, tile) pairs (high half); [1] admitted (query, row) pairs (low
                              // half) and rounds of the exact chain (high half)
 };
+// Per-query allow lists of a shared-row launch (wvg_search_device_pipelined_filtered): the filtered
+// kernels (scan_f32_qshare_filt_kernel, scan_f32_qshare_screen_filt_kernel, qshare_seed_filt_kernel) take
+// this beside QShareArgs, so the unfiltered kernels and their arguments stay as they are.  Query q's word
+// of tile t is allow[q * stride + (t - t0)] if t - t0 < stride (unsigned; t0 wraps for a window that begins
+// before the corpus) and 0 otherwise: a wave-uniform scalar compare and load, so no word outside the
+// caller's [nq][stride] array is read.  A query of the pass scores, and the prologue samples, only the rows
+// of valid & allow_q.  The seed argument above holds with "rows" replaced by "allowed rows": query q's
+// sample is the allowed live rows of the first seed_tiles tiles, all of them among the allowed rows the
+// scan visits for q, so the sample's k-th key is an upper bound of q's filtered result's k-th key; with
+// fewer than k allowed live rows in the sample the seed is KEY_NONE and q's lists start open, beside other
+// queries of the pass whose bounds are closed.  In the screened form a lane's admission mask loses the
+// bits of the queries that do not allow its row: such a pair is never scored and never offered.
+struct QShareFilt {
+    const uint64_t *allow;   // [nq][stride] words, the caller's bitmap in place
+    uint64_t stride;         // words per query
+    uint64_t t0;             // (allow_first_id - id_base) / 64 mod 2^64: the tile of word 0
+};
 bool qshare_supported(int metric, uint32_t dim, int order512);
 // Whether a launch takes the screened form (L2, d = 128, k <= 64, seeded, Tuning::qshare_screen).
 bool qshare_screened(int metric, uint32_t dim, uint32_t k, uint32_t seed_tiles);
@@ -389,8 +407,9 @@ uint32_t qshare_queries_per_pass(uint32_t dim, uint32_t k);
 uint32_t qshare_groups(uint64_t ntiles, int num_cus);
 // Tiles of the prologue's sample for a scan of ntiles tiles by `groups` workgroups (0 = no seeding).
 uint32_t qshare_seed_tiles(uint32_t dim, uint64_t ntiles, uint32_t groups);
-hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s);
-hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s);
+// f: null = the unfiltered kernels; otherwise the filtered ones.
+hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s, const QShareFilt *f = nullptr);
+hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s, const QShareFilt *f = nullptr);
 // Grouped search (wvg_search_group, wvg_group.hip): nq single-query scans, query i
 // over a corpus of its own, as ONE scan launch and one merge launch.  The host
 // writes a descriptor per query and a work-item table; workgroup b of the scan

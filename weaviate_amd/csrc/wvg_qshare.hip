@@ -97,6 +97,16 @@
 // = lane / 4.  B = 4 k-values of the lane's own row; A = the same 4 k-values of
 // query 4 g + (lane & 3) from the LDS image; result register i of the lane = its
 // row's dot with query 4 g + i.
+//
+// Allow lists (wvg_search_device_pipelined_filtered; QShareFilt, wvg_internal.hpp).  The filtered
+// kernels -- scan_f32_qshare_filt_kernel, scan_f32_qshare_screen_filt_kernel, qshare_seed_filt_kernel --
+// are the bodies below with FILT = true and the window as a second kernel argument; the unfiltered
+// kernels instantiate FILT = false and keep their names, arguments and code.  Per tile and query j of the
+// pass mq[j] = valid & allow_j: the allow words are wave-uniform scalar loads behind one window compare,
+// prefetched a tile ahead; query j's keys come from the lanes of mq[j] only (unscreened: lane_key(mq[j]);
+// screened: bit j of the admission mask is cleared elsewhere), and a tile no query of the pass allows is
+// skipped before its rows are loaded.  A row a query does not allow never reaches that query's list, so
+// each list is the one a filtered scan of its own keeps.
 #include <algorithm>
 
 #include "wvg_internal.hpp"
@@ -212,14 +222,23 @@ __device__ __forceinline__ void screen_query_side(const QShareArgs &a, uint32_t 
 // and the scan's chain (chunk_update2 in chunk order, avx256_reduce2,
 // wrap_metric, lane_key: the keys are the scan's bit for bit) -- and writes the
 // sample's k-th smallest key to seeds[q], KEY_NONE with fewer than k live rows.
+// FILT: query q's sample is the rows of valid & allow_q (QShareFilt).
 constexpr int SEED_WAVES = 16;
-template <int METRIC, int D, int E>
-__global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs a)
+
+// Query q's allow word of tile t: wave-uniform, and no word outside [0, stride) is read.
+__device__ __forceinline__ uint64_t allow_word(cu64 *aq, uint64_t stride, uint64_t t0, uint64_t t)
+{
+    const uint64_t w = t - t0;
+    return w < stride ? aq[w] : 0ull;
+}
+
+template <int METRIC, int D, int E, bool FILT>
+__device__ __forceinline__ void qshare_seed_body(const QShareArgs &a, const QShareFilt &f, uint32_t bdim, uint32_t gdim)
 {
     static_assert(D % 32 == 0 && D > 0 && !is_abs_or_neq<METRIC>, "shared rows: fixed D, the AVX2 chains");
     constexpr int NC = D / 4;
     const uint64_t nready = (uint64_t)a.nq * a.groups;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nready; i += (uint64_t)gridDim.x * blockDim.x)
+    for (uint64_t i = (uint64_t)blockIdx.x * bdim + threadIdx.x; i < nready; i += (uint64_t)gdim * bdim)
         a.ready[i] = 0u;
     const uint32_t q = blockIdx.x;  // gridDim.x == nq
     const int lane = threadIdx.x & 63, wave = wave_id();
@@ -240,10 +259,12 @@ __global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs
     }
     const float4 *data = reinterpret_cast<const float4 *>(a.data);
     cu64 *valid = (cu64 *)a.valid;
+    cu64 *aq = FILT ? (cu64 *)f.allow + (size_t)q * f.stride : nullptr;
     WaveTopK<E> tk;
     tk.init((int)a.k);
     for (uint64_t t = a.tile_begin + (uint64_t)wave; t < a.tile_begin + ns; t += SEED_WAVES) {
-        const uint64_t m = valid[t];
+        uint64_t m = valid[t];
+        if constexpr (FILT) m &= allow_word(aq, f.stride, f.t0, t);
         if (m == 0ull) continue;  // wave-uniform
         const float4 *rp = data + (size_t)t * NC * 64 + lane;
         f2v acc[4][4];
@@ -263,6 +284,18 @@ __global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs
     }
     const uint64_t kth = group_combine_kth<E, SEED_WAVES>(tk);
     if (threadIdx.x == 0) a.seeds[q] = kth;
+}
+
+template <int METRIC, int D, int E>
+__global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs a)
+{
+    qshare_seed_body<METRIC, D, E, false>(a, QShareFilt{}, blockDim.x, gridDim.x);  // (read in the kernel: the code of before)
+}
+
+template <int METRIC, int D, int E>
+__global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_filt_kernel(QShareArgs a, QShareFilt f)
+{
+    qshare_seed_body<METRIC, D, E, true>(a, f, blockDim.x, gridDim.x);
 }
 
 // The end of a pass: every wave leaves its QP lists in LDS, then wave w merges
@@ -315,9 +348,13 @@ __device__ __forceinline__ void pass_combine_publish(WaveTopK<E> (&tk)[QP], uint
 // queries (QS_QROW uint4 each), kq = their {Nq2, K1q, K2q, Cq}, m = the tile's
 // validity word.  32 k-steps x 4 query groups of MFMAs; a ds_read_b128 per group
 // feeds two k-steps.
-template <int QP>
+// FILT: mq[j] = the tile's validity word & query j's allow word (subsets of m).  A query whose
+// mq[j] is empty is skipped (wave-uniform) and bit j survives only on the lanes of mq[j]: the
+// scalar word is the lanes' condition where the query is combined, no per-lane copy of it is held.
+template <int QP, bool FILT>
 __device__ __forceinline__ uint32_t screen_tile(const float4 (&xs)[QS_D / 4], const uint4 *qsh, cf4 *kq,
-                                                const WaveTopK<1> (&tk)[QP], uint32_t nqp, uint64_t m, int lane)
+                                                const WaveTopK<1> (&tk)[QP], uint32_t nqp, uint64_t m,
+                                                const uint64_t (&mq)[FILT ? QP : 1], int lane)
 {
     static_assert(QP == 16, "four query groups of four");
     f2v n2a = {0.0f, 0.0f}, n2b = {0.0f, 0.0f};
@@ -351,21 +388,38 @@ __device__ __forceinline__ uint32_t screen_tile(const float4 (&xs)[QS_D / 4], co
     uint32_t adm = 0u;
 #pragma unroll
     for (int j = 0; j < QP; j++) {
-        if ((uint32_t)j < nqp) {  // wave-uniform
+        if ((uint32_t)j < nqp && (!FILT || mq[FILT ? j : 0] != 0ull)) {  // wave-uniform
             const f4v k = kq[j];
             const float t = __builtin_fmaf(-2.0f, acc[j >> 2][j & 3], bx + k.w);
             const float lower = __builtin_fmaf(-k.y, nx, t);
             const float tau_dist = wvg_unord_f32((uint32_t)(tk[j].tau >> 32));  // NaN for an open tau
-            const bool skip = lower > tau_dist && lower < __builtin_inff();
+            bool skip = lower > tau_dist && lower < __builtin_inff();
+            // (the scalar word as the lanes' condition: one scalar AND with the compare's mask)
+            if constexpr (FILT) skip = skip || !__builtin_amdgcn_inverse_ballot_w64(mq[FILT ? j : 0]);
             adm |= skip ? 0u : 1u << j;
         }
     }
+    if constexpr (FILT) return adm;
     return ((m >> lane) & 1ull) ? adm : 0u;
 }
 
+// The allow words of tile t for the nqp queries of a pass (al = the pass's first query's row): one
+// window test for the pass, then a scalar load per query.
+template <int QP>
+__device__ __forceinline__ void pass_allow_words(uint64_t (&aw)[QP], cu64 *al, uint64_t stride, uint64_t t0, uint64_t t,
+                                                 uint32_t nqp)
+{
+    const uint64_t w = t - t0;
+    const bool in = w < stride;  // wave-uniform
+#pragma unroll
+    for (int j = 0; j < QP; j++) aw[j] = in && (uint32_t)j < nqp ? al[(size_t)j * stride + w] : 0ull;
+}
+
 // SCREEN: the bf16 screen per tile, then rounds of the exact chain per admitted row (WHOLE, L2, d = 128, E = 1).
-template <int METRIC, int D, int E, bool WHOLE, bool SCREEN>
-__device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
+// FILT: per tile and query j of the pass mq[j] = valid & query j's allow word (QShareFilt); a tile
+// whose mq[j] are all empty is skipped before its row loads, and query j's keys come from the lanes of mq[j].
+template <int METRIC, int D, int E, bool WHOLE, bool SCREEN, bool FILT>
+__device__ __forceinline__ void qshare_scan_body(const QShareArgs &a, const QShareFilt &f)
 {
     static_assert(D % 32 == 0 && D > 0 && !is_abs_or_neq<METRIC>, "shared rows: fixed D, the AVX2 chains");
     static_assert(!SCREEN || (WHOLE && METRIC == WVG_M_L2 && D == QS_D && E == 1), "the screened form");
@@ -430,11 +484,29 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
             __syncthreads();  // (the last pass's readers are past pass_combine_publish's barriers)
         }
         uint64_t m_next = n ? valid[rev ? t1 - 1 : t0] : 0ull;
+        // FILT: the pass's allow words of the next tile, prefetched with m_next (0 past nqp)
+        cu64 *al = FILT ? (cu64 *)f.allow + (size_t)q0 * f.stride : nullptr;
+        uint64_t aw_next[FILT ? QP : 1], mq[FILT ? QP : 1];
+        if constexpr (FILT) {
+            if (n) pass_allow_words<QP>(aw_next, al, f.stride, f.t0, rev ? t1 - 1 : t0, nqp);
+        }
         for (uint64_t i = 0; i < n; ++i) {
             const uint64_t t = rev ? t1 - 1 - i : t0 + i;
             const uint64_t m = m_next;
-            if (i + 1 < n) m_next = valid[rev ? t - 1 : t + 1];  // scalar prefetch of the next mask
-            if (m == 0ull) continue;  // wave-uniform: nothing live in this tile
+            uint64_t many = m;
+            if constexpr (FILT) {
+                many = 0ull;
+#pragma unroll
+                for (int j = 0; j < QP; j++) {
+                    mq[j] = m & aw_next[j];
+                    many |= mq[j];
+                }
+            }
+            if (i + 1 < n) {  // scalar prefetch of the next mask
+                m_next = valid[rev ? t - 1 : t + 1];
+                if constexpr (FILT) pass_allow_words<QP>(aw_next, al, f.stride, f.t0, rev ? t - 1 : t + 1, nqp);
+            }
+            if (many == 0ull) continue;  // wave-uniform: nothing live (FILT: and allowed for a query of the pass) in this tile
             const float4 *rp = data + (size_t)t * NC * 64 + lane;
             if constexpr (WHOLE) {
                 float4 xs[NC];
@@ -449,7 +521,7 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
                     // Row-level admission: the lane's mask of queries whose lower bound on its row does
                     // not exceed tau, then rounds of the exact chain -- a lane scores its own row against
                     // one of its own admitted queries per round, the query chunks read from LDS.
-                    uint32_t adm = screen_tile<QP>(xs, qsh, (cf4 *)a.qconst + q0, tk, nqp, m, lane);
+                    uint32_t adm = screen_tile<QP, FILT>(xs, qsh, (cf4 *)a.qconst + q0, tk, nqp, m, mq, lane);
 #ifdef WVG_TOOLS
                     n_pairs += nqp;
                     n_adm += (uint32_t)__builtin_popcount(adm);
@@ -514,7 +586,7 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
 #pragma unroll
                                 for (int c = 0; c < 4; c++) qc[c] = qn[c];
                             }
-                            tk[j].offer_bounded(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane),
+                            tk[j].offer_bounded(lane_key(FILT ? mq[FILT ? j : 0] : m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane),
                                                 [&] { return seed_bound(sd + j); });
                         }
                     }
@@ -551,7 +623,7 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a)
 #pragma unroll
                 for (int j = 0; j < QP; j++)
                     if ((uint32_t)j < nqp)
-                        tk[j].offer_bounded(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc[j])), t, lane),
+                        tk[j].offer_bounded(lane_key(FILT ? mq[FILT ? j : 0] : m, wrap_metric(a.metric, avx256_reduce2(acc[j])), t, lane),
                                             [&] { return seed_bound(sd + j); });
             }
         }
@@ -588,14 +660,27 @@ template <int METRIC, int D, int E, bool WHOLE>
 __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_kernel(
     QShareArgs a)
 {
-    qshare_scan_body<METRIC, D, E, WHOLE, false>(a);
+    qshare_scan_body<METRIC, D, E, WHOLE, false, false>(a, QShareFilt{});
+}
+
+template <int METRIC, int D, int E, bool WHOLE>
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_filt_kernel(
+    QShareArgs a, QShareFilt f)
+{
+    qshare_scan_body<METRIC, D, E, WHOLE, false, true>(a, f);
 }
 
 // The screened form: L2, d = 128, k <= 64, whole rows.
 __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_screen_kernel(
     QShareArgs a)
 {
-    qshare_scan_body<WVG_M_L2, QS_D, 1, true, true>(a);
+    qshare_scan_body<WVG_M_L2, QS_D, 1, true, true, false>(a, QShareFilt{});
+}
+
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_screen_filt_kernel(
+    QShareArgs a, QShareFilt f)
+{
+    qshare_scan_body<WVG_M_L2, QS_D, 1, true, true, true>(a, f);
 }
 
 // Which corpora the kernel covers, its queries per pass and its grid.
@@ -649,37 +734,54 @@ bool qshare_screened(int metric, uint32_t dim, uint32_t k, uint32_t seed_tiles)
 }
 
 template <int METRIC, int E>
-static hipError_t launch_seed_e(const QShareArgs &a, hipStream_t s)
+static hipError_t launch_seed_e(const QShareArgs &a, hipStream_t s, const QShareFilt *f)
 {
     dim3 grid(a.nq), block(SEED_WAVES * 64);
-    if (a.dim == 128)
+    if (a.dim != 128 && a.dim != 768) return hipErrorInvalidValue;
+    if (f) {
+        if (a.dim == 128)
+            hipLaunchKernelGGL((qshare_seed_filt_kernel<METRIC, 128, E>), grid, block, 0, s, a, *f);
+        else
+            hipLaunchKernelGGL((qshare_seed_filt_kernel<METRIC, 768, E>), grid, block, 0, s, a, *f);
+    } else if (a.dim == 128) {
         hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 128, E>), grid, block, 0, s, a);
-    else if (a.dim == 768)
+    } else {
         hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 768, E>), grid, block, 0, s, a);
-    else
-        return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s)
+hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s, const QShareFilt *f)
 {
     if (!qshare_supported(a.metric, a.dim, 0) || a.nq == 0) return hipErrorInvalidValue;
     auto go = [&](auto M) -> hipError_t {
         constexpr int MM = decltype(M)::value;
-        if (a.k <= 64) return launch_seed_e<MM, 1>(a, s);
-        if (a.k <= 128) return launch_seed_e<MM, 2>(a, s);
-        return launch_seed_e<MM, 4>(a, s);
+        if (a.k <= 64) return launch_seed_e<MM, 1>(a, s, f);
+        if (a.k <= 128) return launch_seed_e<MM, 2>(a, s, f);
+        return launch_seed_e<MM, 4>(a, s, f);
     };
     return a.metric == WVG_M_L2 ? go(MetricTag<WVG_M_L2>{}) : go(MetricTag<WVG_M_DOT>{});
 }
 
 template <int METRIC, int E>
-static hipError_t launch_qshare_e(const QShareArgs &a, uint32_t mergers, hipStream_t s)
+static hipError_t launch_qshare_e(const QShareArgs &a, uint32_t mergers, hipStream_t s, const QShareFilt *f)
 {
     dim3 grid(a.groups + mergers), block(SCAN_WAVES * 64);
     if (a.screen) {
         if (METRIC != WVG_M_L2 || E != 1 || a.dim != QS_D || !a.qbf || !a.qconst) return hipErrorInvalidValue;
-        launch_timed(scan_f32_qshare_screen_kernel, grid, block, 0, s, a);
+        if (f)
+            launch_timed(scan_f32_qshare_screen_filt_kernel, grid, block, 0, s, a, *f);
+        else
+            launch_timed(scan_f32_qshare_screen_kernel, grid, block, 0, s, a);
+        return hipGetLastError();
+    }
+    if (f) {  // the filtered forms: whole rows at d = 128, blocks at d = 768
+        if (a.dim == 128)
+            launch_timed((scan_f32_qshare_filt_kernel<METRIC, 128, E, true>), grid, block, 0, s, a, *f);
+        else if (a.dim == 768)
+            launch_timed((scan_f32_qshare_filt_kernel<METRIC, 768, E, false>), grid, block, 0, s, a, *f);
+        else
+            return hipErrorInvalidValue;
         return hipGetLastError();
     }
     if (a.dim == 128) {
@@ -698,14 +800,14 @@ static hipError_t launch_qshare_e(const QShareArgs &a, uint32_t mergers, hipStre
     return hipGetLastError();
 }
 
-hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s)
+hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s, const QShareFilt *f)
 {
     if (!qshare_supported(a.metric, a.dim, 0) || mergers == 0) return hipErrorInvalidValue;
     auto go = [&](auto M) -> hipError_t {
         constexpr int MM = decltype(M)::value;
-        if (a.k <= 64) return launch_qshare_e<MM, 1>(a, mergers, s);
-        if (a.k <= 128) return launch_qshare_e<MM, 2>(a, mergers, s);
-        return launch_qshare_e<MM, 4>(a, mergers, s);
+        if (a.k <= 64) return launch_qshare_e<MM, 1>(a, mergers, s, f);
+        if (a.k <= 128) return launch_qshare_e<MM, 2>(a, mergers, s, f);
+        return launch_qshare_e<MM, 4>(a, mergers, s, f);
     };
     return a.metric == WVG_M_L2 ? go(MetricTag<WVG_M_L2>{}) : go(MetricTag<WVG_M_DOT>{});
 }

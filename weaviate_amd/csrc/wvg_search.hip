@@ -1381,9 +1381,12 @@ int wvg_search_device_check(wvg_ctx *ctx, void *d_workspace, void *stream)
     return fail(WVG_ERR_DEVICE, "device search status " + std::to_string(st));
 }
 
-int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k, uint64_t *d_ids,
-                                float *d_dists, uint32_t *d_counts, void *d_workspace, size_t workspace_bytes,
-                                void *stream)
+// wvg_search_device_pipelined and wvg_search_device_pipelined_filtered.  flt: null = no filter; otherwise
+// the caller's per-query allow words on the device (QShareFilt: never read by the host, so the scanned
+// tile range is the corpus's own and the kernels apply the window).
+static int search_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k, const QShareFilt *flt,
+                            uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
+                            size_t workspace_bytes, void *stream)
 {
     if (!c) return fail(WVG_ERR_INVALID, "null corpus");
     if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "k above 256 is not supported by the fused top-k");
@@ -1393,8 +1396,8 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
     hipStream_t s = (hipStream_t)stream;
     std::shared_lock<std::shared_mutex> lk(c->rw);
     SearchPlan p = plan_search(c, 1, k, nullptr, 0);
-    if (p.empty) {  // empty corpus / slab: empty results, as wvg_search's write_empty
-        WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));
+    if (p.empty || (flt && flt->stride == 0)) {  // empty corpus / slab, or an empty window: empty results, as
+        WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));  // wvg_search's write_empty
         return WVG_OK;
     }
     if (tuning().pipeline_mode == 1 && qshare_route(c, nq)) {  // shared rows: one launch, rows read once per pass
@@ -1436,10 +1439,44 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
             a.qconst = (float4 *)(w + l.qconst);
             a.screen_count = (uint64_t *)(w + l.count);
         }
-        WVG_HIP(launch_qshare_seed(a, s));  // zeroes the ready words, writes the seeds
+        WVG_HIP(launch_qshare_seed(a, s, flt));  // zeroes the ready words, writes the seeds
         ProfArm arm(c->ctx);
         if (arm.rc) return arm.rc;
-        WVG_HIP(launch_scan_f32_qshare(a, mergers, s));
+        WVG_HIP(launch_scan_f32_qshare(a, mergers, s, flt));
+        return WVG_OK;
+    }
+    if (flt && nq > 1) {
+        // Filtered queries the shared-row kernel does not cover (other metrics or dims, order512,
+        // cache_reuse = 0): K1 with one allow window per query (ScanArgs::allow_qstride), then the K2
+        // merge, on the caller's stream; the partial lists lie where the query stream's would.
+        const StreamLayout l = stream_layout(p, nq, k);
+        if (!d_workspace || workspace_bytes < l.total) return fail(WVG_ERR_INVALID, "workspace too small");
+        uint64_t *partials = (uint64_t *)((char *)d_workspace + l.partials);
+        ScanArgs a{};
+        a.data = c->d_data;
+        a.valid = c->d_valid;
+        a.allow = flt->allow;
+        a.allow_words = flt->stride;
+        a.allow_t0 = flt->t0;
+        a.allow_qstride = flt->stride;
+        a.id_base = c->id_base;
+        a.tile_begin = p.tb;
+        a.tile_end = p.te;
+        a.dim = c->dim;
+        a.nchunks = c->nchunks;
+        a.metric = c->metric;
+        a.queries = d_queries;
+        a.qpitch = c->dim;
+        a.nq = nq;
+        a.k = k;
+        a.reverse = next_direction(c, 1);
+        a.order512 = c->ctx->order512;
+        a.plain = plain_loads(c, p.tb, p.te);
+        a.cache_tail256 = k1_cache_tail(c, p.tb, p.te);
+        ProfArm arm(c->ctx);
+        if (arm.rc) return arm.rc;
+        WVG_HIP(launch_scan_f32(a, partials, p.groups, s));
+        WVG_HIP(launch_merge_lists(partials, nq, (uint32_t)p.groups, k, k, c->id_base, d_ids, d_dists, d_counts, s));
         return WVG_OK;
     }
     if (tuning().pipeline_mode == 1) {  // query-stream kernel: one launch for all nq queries, a full scan each
@@ -1473,6 +1510,11 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
         a.order512 = c->ctx->order512;
         a.plain = plain_loads(c, p.tb, p.te);
         a.cache_tail256 = k1_cache_tail(c, p.tb, p.te);
+        if (flt) {  // one filtered query (nq = 1): the scan's allow window
+            a.allow = flt->allow;
+            a.allow_words = flt->stride;
+            a.allow_t0 = flt->t0;
+        }
         j.row_split = (tuning().stream_variant & 1) == 0;
         if ((tuning().stream_variant & 2) == 0) {  // per-list hand-offs; the words are zeroed with the counters
             j.ready = (uint32_t *)(w + l.ready);
@@ -1486,6 +1528,7 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
     }
 #ifdef WVG_TOOLS
     // A/B (pipeline_mode 0): one scan launch per query, query i's launch merging query i-1
+    if (flt) return fail(WVG_ERR_UNSUPPORTED, "pipeline mode 0 takes no allow lists");
     const size_t half = align_up(p.workspace_bytes(1, k), 256);
     if (!d_workspace || workspace_bytes < WS_STATUS_BYTES + 2 * half) return fail(WVG_ERR_INVALID, "workspace too small");
     char *w0 = (char *)d_workspace + WS_STATUS_BYTES;
@@ -1525,6 +1568,28 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
 #else
     return fail(WVG_ERR_UNSUPPORTED, "pipeline mode");
 #endif
+}
+
+int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k, uint64_t *d_ids,
+                                float *d_dists, uint32_t *d_counts, void *d_workspace, size_t workspace_bytes,
+                                void *stream)
+{
+    return search_pipelined(c, d_queries, nq, k, nullptr, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
+}
+
+int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
+                                         const uint64_t *d_allow, uint64_t allow_stride, uint64_t allow_first_id,
+                                         uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
+                                         size_t workspace_bytes, void *stream)
+{
+    if (!d_allow)  // no filter: wvg_search_device_pipelined exactly
+        return search_pipelined(c, d_queries, nq, k, nullptr, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
+    if (!c) return fail(WVG_ERR_INVALID, "null corpus");
+    if (allow_first_id % 64 != 0) return fail(WVG_ERR_INVALID, "allow_first_id must be a multiple of 64");
+    // word 0 is the word of tile (allow_first_id - id_base) / 64, modulo 2^64 for a window that begins
+    // before the corpus (id_base is a multiple of 64): the kernels test t - t0 < stride unsigned
+    QShareFilt f{d_allow, allow_stride, allow_first_id / 64 - c->id_base / 64};
+    return search_pipelined(c, d_queries, nq, k, &f, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
 }
 
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k, uint64_t *d_ids, float *d_dists,

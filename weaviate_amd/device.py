@@ -92,6 +92,19 @@ def allow_bitmap(ids, n_bits: int | None = None) -> np.ndarray:
     return words
 
 
+def allow_window(id_lists, first_id: int, stride: int) -> np.ndarray:
+    """Per-query allow lists -> the [nq][stride] window wvg_search_device_pipelined_filtered reads: bit b of
+    word w of row q = docID first_id + 64 w + b (first_id a multiple of 64); ids outside the window are dropped."""
+    if first_id % 64:
+        raise ValueError("first_id must be a multiple of 64")
+    out = np.zeros((len(id_lists), stride), dtype=np.uint64)
+    for q, ids in enumerate(id_lists):
+        ids = np.asarray(list(ids), dtype=np.uint64)
+        ids = ids[(ids >= np.uint64(first_id)) & (ids < np.uint64(first_id + 64 * stride))] - np.uint64(first_id)
+        np.bitwise_or.at(out[q], (ids >> np.uint64(6)).astype(np.int64), np.left_shift(np.uint64(1), ids & np.uint64(63)))
+    return out
+
+
 class Corpus:
     """A device-resident corpus (wvg_corpus_*): F32 rows, BQ codes or PQ codes."""
 
@@ -222,6 +235,19 @@ class Corpus:
         check(self.lib.wvg_search(self.handle, fptr(q), nq, k, u64ptr(aw) if aw is not None else None, an,
                                   u64ptr(ids), fptr(dists), u32ptr(counts)))
         return ids, dists, counts
+
+    def search_device_pipelined(self, d_queries: int, nq: int, k: int, d_ids: int, d_dists: int, d_counts: int,
+                                d_workspace: int, workspace_bytes: int, stream: int = 0, d_allow: int = 0,
+                                allow_stride: int = 0, allow_first_id: int = 0) -> None:
+        """wvg_search_device_pipelined on device pointers, asynchronous on `stream`; with d_allow (device
+        words [nq][allow_stride], see allow_window) wvg_search_device_pipelined_filtered."""
+        if not d_allow:
+            check(self.lib.wvg_search_device_pipelined(self.handle, d_queries, nq, k, d_ids, d_dists, d_counts,
+                                                       d_workspace, workspace_bytes, stream))
+        else:
+            check(self.lib.wvg_search_device_pipelined_filtered(self.handle, d_queries, nq, k, d_allow, allow_stride,
+                                                                allow_first_id, d_ids, d_dists, d_counts, d_workspace,
+                                                                workspace_bytes, stream))
 
     def search_by_distance(self, query, target: float, max_limit: int = -1, allow=None, capacity: int | None = None):
         """wvg_search_by_distance: (ids, dists) of every row within `target`

@@ -150,7 +150,8 @@ class ShardedFlatIndex:
             b.ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
         return b
 
-    def search_device(self, q: torch.Tensor, k: int, stream=None, pipelined: bool = False):
+    def search_device(self, q: torch.Tensor, k: int, stream=None, pipelined: bool = False, allow=None,
+                      allow_first_id: int = 0):
         """q: [nq][dim] float32 on this rank's GPU (normalized for cosine).
         Returns (ids int64 [nq][k] global docIDs, dists [nq][k], counts [nq]).
         stream: the stream every step runs on (a torch.cuda.Stream or a raw
@@ -159,13 +160,31 @@ class ShardedFlatIndex:
         allocations are all ordered on it, so a caller's side stream needs no
         extra synchronisation.  pipelined: nq independent single-query scans
         in one launch (wvg_search_device_pipelined) instead of one batched
-        search."""
+        search.  allow (pipelined only): one allow list per query, a uint64 or
+        int64 tensor [nq][stride] on the GPU whose bit b of word w stands for
+        docID allow_first_id + 64 w + b (wvg_search_device_pipelined_filtered);
+        every rank passes the same window and applies it to its own slab."""
         nq = q.shape[0]
         dev = q.device
         s_obj, s_raw = _stream_obj(stream, dev)
         grouped = dist.is_initialized()  # a group of any size (one included) exchanges through it
         world = dist.get_world_size(self.group) if grouped else 1
         fn = self.lib.wvg_search_device_pipelined if pipelined else self.lib.wvg_search_device
+        if allow is not None:
+            if not pipelined:
+                raise ValueError("allow lists need pipelined=True")
+            if allow.dim() != 2 or allow.shape[0] != nq or allow.element_size() != 8 or not allow.is_contiguous() \
+                    or allow.device != dev:
+                raise ValueError("allow: a contiguous [nq][stride] tensor of 64-bit words on the queries' device")
+            filt, a_ptr, a_stride = self.lib.wvg_search_device_pipelined_filtered, allow.data_ptr(), allow.shape[1]
+            if a_stride:
+
+                def fn(c, qp, n, kk, *rest):
+                    return filt(c, qp, n, kk, a_ptr, a_stride, allow_first_id, *rest)
+            else:  # an empty window (no pointer to pass): nothing is allowed
+
+                def fn(c, qp, n, kk, *rest):
+                    return filt(c, qp, n, kk, b.ws.data_ptr(), 0, allow_first_id, *rest)
         with torch.cuda.stream(s_obj):
             b = self._buffers(nq, k, dev, world)
             if not grouped:

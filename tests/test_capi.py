@@ -200,6 +200,52 @@ def test_k1_matrix_covers_every_specialization(tmp_path):
         assert {a[2] for f, a in found if f == fam} == {1, 2, 4}, fam
 
 
+def _k5_instantiations(lib_path, tmp_path, readelf):
+    """{(kernel, (template arguments...))} of scan_bq_kernel<E, NCH, COS, EMIT> and
+    scan_bq_group_kernel<NCH> in the library's gfx950 code objects, parsed from the mangled
+    kernel names (...scan_bq_kernelILi<E>ELi<NCH>ELb<COS>ELi<EMIT>EE...)."""
+    import subprocess
+
+    found = set()
+    for j, co in enumerate(_gfx950_code_objects(lib_path)):
+        f = tmp_path / f"k5co{j}.o"
+        f.write_bytes(co)
+        notes = subprocess.run([readelf, "--notes", str(f)], capture_output=True, text=True).stdout
+        for ln in notes.splitlines():
+            ln = ln.strip()
+            if not ln.startswith(".name:"):
+                continue
+            m = re.search(r"\d+(scan_bq_(?:group_)?kernel)I((?:L[ib]\d+E)+)E", ln)
+            if m:
+                found.add((m.group(1), tuple(int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2)))))
+    return found
+
+
+def test_k5_matrix_covers_every_specialization(tmp_path):
+    """The chunk counts, list sizes and record modes scan_bq_kernel is compiled for are exactly
+    those tests/test_gpu_bq_k5_matrix.py runs against the oracle, each fixed chunk count with an
+    even and an odd word count: a new `case N:` of launch_bq_ec (or of the group kernel's
+    dispatch) fails here until the matrix has rows for it."""
+    import itertools
+
+    from test_gpu_bq_k5_matrix import DIMS, K5, nch_of, words_of
+    from weaviate_amd import _lib
+
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not os.path.exists(readelf):
+        pytest.skip("llvm-readelf not available")
+    found = _k5_instantiations(_lib.LIB_PATH, tmp_path, readelf)
+    assert K5 == {"nch": (1, 6, 12), "e": (1, 2, 4), "emit": (0, 1, 2)}
+    nchs = set(K5["nch"]) | {0}
+    scan = {a for f, a in found if f == "scan_bq_kernel"}
+    assert scan == set(itertools.product(K5["e"], nchs, (0, 1), K5["emit"])), sorted(scan)
+    assert len(scan) == 72
+    assert {a for f, a in found if f == "scan_bq_group_kernel"} == {(n,) for n in nchs}
+    for nch in K5["nch"]:  # every fixed chunk count runs with an even and with an odd word count
+        assert {words_of(d) % 2 for d in DIMS if nch_of(d) == nch} == {0, 1}, nch
+    assert any(nch_of(d) == 0 for d in DIMS)  # and the generic loop
+
+
 def _screen_instantiations(lib_path, tmp_path, readelf):
     """{(kernel, (template arguments...))} of the batched screen's scoring kernels -- every
     kernel that takes a ScreenArgs -- in the library's gfx950 code objects, parsed from the

@@ -143,7 +143,8 @@ def check_candidates(tenants, which, qs, R, allows=None, allowed=None, separate=
 
 
 # ---- 1. equality with separate calls and with the oracle -----------------------------
-@pytest.mark.parametrize("d", [64, 200, 768, 1536])  # NCH 1, generic (2 chunks), 6, 12
+# NCH 1, generic (2 chunks), 6, 12; then odd word counts (3 / 11 / 23 words) under the generic, 6 and 12 kernels
+@pytest.mark.parametrize("d", [64, 200, 768, 1536, 130, 700, 1440])
 @pytest.mark.parametrize("metric", [METRIC_L2, METRIC_DOT, METRIC_COSINE])
 def test_equals_separate_calls_and_oracle(ctx, orc, metric, d):
     tenants = make_tenants(ctx, orc, metric, d, 7000 + 13 * d + metric)

@@ -9,7 +9,8 @@ equal to the oracle's restatement of the heap (oracle/wv_oracle.c
 insert_to_heap / heap_pop / extract_heap), on inputs built to tie heavily --
 small d (Hamming 0..64), integer rows (ties in the exact distances too),
 batches (the co-scheduled K5 grid), allow lists, deletes, and a docID order
-that overflows the per-wave buffers (the rerun path).
+on which a wave records every row it scans (the rerun after an overflow runs
+in tests/test_gpu_bq_k5_matrix.py).
 """
 import ctypes
 
@@ -153,8 +154,16 @@ def test_bq_rescore_integer_rows_ties_in_both_heaps(ctx, orc, metric):
 def test_bq_candidates_overflow_rerun(ctx, orc):
     """Distances falling with the docID (1536 - id mod 1500 set bits against an
     all-zero query code): every row of a wave beats the wave's own running
-    R-th, so the per-wave buffers overflow and the query is rerun with
-    full-size buffers seeded from the first pass -- still the heap's result."""
+    R-th, so every row is recorded -- still the heap's result.
+
+    Written to overflow the per-wave buffers; at 256 CUs it does not.  The
+    scan runs 256 groups = 1024 waves over 6250 tiles, at most 7 tiles = 448
+    rows per wave, and emit_plan_for (wvg_replay.hip:480-497) gives each wave
+    an LDS record of 512 keys; the prefix filter keeps far fewer than
+    REPLAY_OUT_CAP rows per query.  A traced run (profiles/r15/bq_k5_matrix/)
+    launched scan_bq_kernel<1 | 4, 12, false | true, 1> and ordkeys_bq_kernel
+    (R = 600) only: full LDS records, no rerun.  The rerun itself is reached by
+    tests/test_gpu_bq_k5_matrix.py::test_bq_rerun_reached."""
     n, d = 400_000, 1536
     w = d // 64
     nb = (1536 - (np.arange(n) % 1500)).astype(np.int64)

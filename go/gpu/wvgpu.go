@@ -963,6 +963,31 @@ func (x *Corpus) SearchDevicePipelined(b DeviceBuffers, nq, k int) error {
 		b.Stream))
 }
 
+// StreamPlan tells what SearchDevicePipelined(nq, k) will do (struct
+// wvg_stream_plan): a caller that batches queries fills whole passes.
+type StreamPlan struct {
+	SharedRows     bool // the shared-row kernel; false: one scan of the corpus per query
+	QueriesPerPass int  // queries that share one read of the rows (1 without SharedRows)
+	Passes         int  // reads of the corpus the call makes
+	Seeded         bool // the prologue samples rows
+	Screened       bool // the bf16 screen runs
+}
+
+// DevicePipelinedPlan: the StreamPlan of a call with nq queries and k results
+// each.  Host only: nothing is launched.
+func (x *Corpus) DevicePipelinedPlan(nq, k int) (StreamPlan, error) {
+	defer pin(x)()
+	if nq < 0 || k < 0 {
+		return StreamPlan{}, errors.New("wvgpu: negative nq or k")
+	}
+	var sp C.wvg_stream_plan
+	if e := err(C.wvg_search_device_pipelined_plan(x.h, C.uint32_t(nq), C.uint32_t(k), &sp)); e != nil {
+		return StreamPlan{}, e
+	}
+	return StreamPlan{SharedRows: sp.shared_rows != 0, QueriesPerPass: int(sp.queries_per_pass),
+		Passes: int(sp.passes), Seeded: sp.seeded != 0, Screened: sp.screened != 0}, nil
+}
+
 // DeviceAllow is a window of per-query allow lists in HBM for
 // SearchDevicePipelinedFiltered: Words holds [nq][Stride] uint64 and bit b of
 // word w of query q's row stands for docID FirstID + 64*w + b; docIDs outside

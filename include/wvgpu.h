@@ -334,20 +334,22 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
 /* nq single-query searches (flat.SearchByVector per query, as concurrent
  * Weaviate queries issue them) in ONE launch.  The results are those of nq
  * independent searches, bit for bit.  Where the shared-row kernel applies
- * -- nq >= 2, an L2 / dot / cosine corpus of d = 128 or 768 in the AVX2
- * distance order, cache_reuse on -- the rows are read once per pass of up to
- * 16 queries (k <= 64; 8 for k <= 128, 4 above; d = 768: 4, 2 above 128) and
+ * -- nq >= 2, an L2 / dot / cosine corpus of any d >= 8 (a multiple of 4, as
+ * device search requires) in the AVX2 distance order, cache_reuse on -- the
+ * rows are read once per pass of up to 16 queries at d = 128 (k <= 64; 8 for
+ * k <= 128, 4 above) and of 4 queries at every other d (2 for k > 128), and
  * every query of the pass is scored against each row while it is in
  * registers; one merge workgroup per query merges its partial lists in the
  * same launch.  A short prologue launch on the same stream prepares that
  * scan's part of the workspace (its hand-off words and, where every wave
  * scans only a few tiles, per query the k-th distance of a sample of the
  * first rows, which bounds the scan's lists from the start; the results do
- * not depend on it).  Everywhere else (one query, other metrics or dims,
- * cache_reuse = 0) every query is one full scan of the corpus: the scan
- * workgroups walk the queries back to back and one extra workgroup merges
- * each query's lists while the scan moves on.  F32 corpora; same workspace
- * size rule; outputs as wvg_search_device.                                 */
+ * not depend on it).  Everywhere else (one query, other metrics, d = 4, the
+ * AVX-512 order, cache_reuse = 0) every query is one full scan of the corpus:
+ * the scan workgroups walk the queries back to back and one extra workgroup
+ * merges each query's lists while the scan moves on.  F32 corpora; same
+ * workspace size rule; outputs as wvg_search_device.
+ * wvg_search_device_pipelined_plan tells which of the two a call takes.    */
 int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                                 uint64_t *d_ids, float *d_dists, uint32_t *d_counts,
                                 void *d_workspace, size_t workspace_bytes, void *stream);
@@ -371,7 +373,7 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
  * (see above) the filtered queries share each row read like unfiltered ones:
  * a query scores only the rows its list allows, and a 64-row tile that no
  * query of the pass allows is skipped before it is read.  Everywhere else
- * (one query, other metrics or dims, cache_reuse = 0) every query is one scan
+ * (one query, other metrics, d = 4, cache_reuse = 0) every query is one scan
  * with its own window, followed by a merge launch for nq >= 2.  Otherwise as
  * wvg_search_device_pipelined: F32 corpora, asynchronous on `stream`, no
  * allocation, no host synchronization, capturable; the same workspace rule
@@ -381,6 +383,20 @@ int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, 
                                          uint64_t allow_first_id, uint64_t *d_ids, float *d_dists,
                                          uint32_t *d_counts, void *d_workspace, size_t workspace_bytes,
                                          void *stream);
+/* What wvg_search_device_pipelined(c, ..., nq, k, ...) will do, for a caller
+ * that sizes its batches to fill whole passes.  Host only: no device call,
+ * nothing launched; computed by the functions the search itself routes with.
+ * With an allow list the same call shares rows under the same conditions.
+ * nq == 0, k == 0 or an empty corpus: passes = 0.  Errors as the search's
+ * (k > 256, a corpus that is not F32, dim % 4 != 0).                        */
+typedef struct wvg_stream_plan {
+    uint32_t shared_rows;      /* 1: the shared-row kernel; 0: one scan per query */
+    uint32_t queries_per_pass; /* queries that share one read of the rows (1 if !shared_rows) */
+    uint32_t passes;           /* reads of the corpus the call makes */
+    uint32_t seeded;           /* the prologue samples rows */
+    uint32_t screened;         /* the bf16 screen runs */
+} wvg_stream_plan;
+int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg_stream_plan *out);
 /* Synchronizes `stream` and reads (and clears) the workspace's sticky status
  * word: WVG_ERR_DEVICE if any device search on this workspace since the last
  * check could not complete -- the query-stream merge workgroup of

@@ -39,6 +39,12 @@ class Options(ctypes.Structure):
                 ("heap_replay", ctypes.c_int32)]
 
 
+class StreamPlan(ctypes.Structure):
+    """struct wvg_stream_plan (include/wvgpu.h): what a wvg_search_device_pipelined call will do."""
+    _fields_ = [("shared_rows", c_uint32), ("queries_per_pass", c_uint32), ("passes", c_uint32),
+                ("seeded", c_uint32), ("screened", c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/wvgpu.h.
 _P = POINTER
 SIGNATURES = {
@@ -99,6 +105,7 @@ SIGNATURES = {
     "wvg_search_device_pipelined_filtered": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint64,
                                                      c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                                      c_void_p]),
+    "wvg_search_device_pipelined_plan": (c_int, [c_void_p, c_uint32, c_uint32, _P(StreamPlan)]),
     "wvg_topk_merge_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "wvg_search_device_check": (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -329,8 +329,9 @@ struct StreamJob {
 };
 hipError_t launch_scan_f32_stream(const ScanArgs &a, const StreamJob &j, hipStream_t s);
 // Shared-row query stream (scan_f32_qshare_kernel): L2 / dot / cosine F32 corpora
-// of d = 128 or 768 in the AVX2 order, nq >= 2, with or without per-query allow
-// lists (QShareFilt below).  One launch of
+// of d >= 8 (d % 4 == 0) in the AVX2 order, nq >= 2, with or without per-query allow
+// lists (QShareFilt below); d = 128 and 768 have fixed-dimension forms, every other
+// d runs scan_f32_qshare_dyn_kernel, unseeded and unscreened.  One launch of
 // `groups` scan workgroups + `mergers` merge workgroups.  The queries are taken
 // qshare_queries_per_pass() at a time; a pass walks the wave's tiles once
 // (direction (reverse + pass) & 1) and scores every query of the pass against each
@@ -630,7 +631,8 @@ struct Tuning {
                                   // replaces the K3b pilot (0 = the K3b pilot; A/B)
     int qshare = 0;          // wvg_search_device_pipelined's shared-row kernel (tuning key 34): 0 = where it applies,
                              // -1 = never (one full scan per query, scan_f32_stream_kernel), 2 = its block shape
-                             // (4 queries per pass) at d = 128 too (A/B)
+                             // (4 queries per pass) at d = 128 too (A/B), 3 = the runtime-dimension form at
+                             // d = 128 and 768 too (A/B against their fixed forms)
     int qshare_mergers = 0;  // its merge workgroups (tuning key 35): 0 = one per query (at most 64), n = n (1 = the
                              // queries merged one after another; A/B)
     int qshare_seed = 32;    // shared-row scan (tuning key 37): tiles of the prologue's row sample whose k-th key

@@ -11,6 +11,11 @@
 //  blocks (d = 768, and d = 128 in the tools build for A/B): K1Q's body -- a
 //    32-float block of the row is loaded and folded into the QP queries' chains
 //    (QP x 32 accumulators live through the row).
+//  runtime dimension (scan_f32_qshare_dyn_kernel: every other d >= 8, d % 4 == 0):
+//    the block shape with a.dim >> 5 blocks, then the tail of the AVX2 order as
+//    row_dot_or_l2_generic (wvg_rowdist.hpp) walks it -- the leftover 8-float
+//    blocks into accumulator row 0, four last elements through scalar_update
+//    into the sum avx256_reduce adds last.  Unseeded and unscreened.
 // The query words and tile masks are wave-uniform and read through the constant
 // address space: the publishes of the previous pass would otherwise make them
 // "maybe clobbered" vector loads (wvg_topk.hpp, offer_dist_emit).  Nothing
@@ -140,7 +145,7 @@ __device__ __forceinline__ void chunk_update2(f2v (&acc)[4][4], int cc, f4v q, f
     }
 }
 
-__device__ __forceinline__ float avx256_reduce2(const f2v (&acc2)[4][4])
+__device__ __forceinline__ float avx256_reduce2(const f2v (&acc2)[4][4], float sum = 0.0f)  // sum: the scalar tail's
 {
     float acc[4][8];
 #pragma unroll
@@ -150,7 +155,7 @@ __device__ __forceinline__ float avx256_reduce2(const f2v (&acc2)[4][4])
             acc[r][2 * p] = acc2[r][p].x;
             acc[r][2 * p + 1] = acc2[r][p].y;
         }
-    return avx256_reduce(acc, 0.0f);
+    return avx256_reduce(acc, sum);
 }
 
 // Four chunks (16 floats, one scalar load) of a query.
@@ -161,10 +166,11 @@ __device__ __forceinline__ void ld_granule(f4v (&q)[4], cf4 *p)
 }
 
 // Queries per pass: what fits beside the row registers without scratch
-// (WHOLE: 128 row + 32 accumulator registers + 2 E per query).
+// (WHOLE: 128 row + 32 accumulator registers + 2 E per query).  d = 0: the
+// runtime-dimension block form, the shape of d = 768.
 constexpr int qshare_qp(int d, int e, bool whole)
 {
-    return whole ? (e == 1 ? 16 : (e == 2 ? 8 : 4)) : (d > 128 && e == 4 ? 2 : 4);
+    return whole ? (e == 1 ? 16 : (e == 2 ? 8 : 4)) : ((d == 0 || d > 128) && e == 4 ? 2 : 4);
 }
 
 // The bound of a query's lists from its seed: seed + 1, so that `key < bound`
@@ -298,6 +304,16 @@ __global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_filt_kernel(QShar
     qshare_seed_body<METRIC, D, E, true>(a, f, blockDim.x, gridDim.x);
 }
 
+// The prologue without a sample (the runtime-dimension form runs unseeded): the
+// ready words zeroed, every seed open.
+__global__ __launch_bounds__(SEED_WAVES * 64) void qshare_open_seed_kernel(QShareArgs a)
+{
+    const uint64_t nready = (uint64_t)a.nq * a.groups;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nready; i += (uint64_t)gridDim.x * blockDim.x)
+        a.ready[i] = 0u;
+    if (threadIdx.x == 0) a.seeds[blockIdx.x] = WVG_KEY_NONE;  // gridDim.x == nq
+}
+
 // The end of a pass: every wave leaves its QP lists in LDS, then wave w merges
 // the SCAN_WAVES lists of the pass's queries w, w + SCAN_WAVES, ... and publishes
 // each as group_combine_publish does (write-through stores, the storing wave's
@@ -421,10 +437,12 @@ __device__ __forceinline__ void pass_allow_words(uint64_t (&aw)[QP], cu64 *al, u
 template <int METRIC, int D, int E, bool WHOLE, bool SCREEN, bool FILT>
 __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a, const QShareFilt &f)
 {
-    static_assert(D % 32 == 0 && D > 0 && !is_abs_or_neq<METRIC>, "shared rows: fixed D, the AVX2 chains");
+    static_assert(D % 32 == 0 && D >= 0 && !is_abs_or_neq<METRIC>, "shared rows: fixed D (0 = a.dim), the AVX2 chains");
     static_assert(!SCREEN || (WHOLE && METRIC == WVG_M_L2 && D == QS_D && E == 1), "the screened form");
+    static_assert(D > 0 || !WHOLE, "the runtime dimension takes the block shape");
     constexpr int QP = qshare_qp(D, E, WHOLE);
     constexpr int NC = D / 4;
+    const int nb = D ? D / 32 : (int)(a.dim >> 5);  // 32-float blocks of a row
     const uint32_t G = a.groups;
     if (blockIdx.x >= G) {
         const uint32_t nm = gridDim.x - G;
@@ -507,7 +525,7 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a, const QSha
                 if constexpr (FILT) pass_allow_words<QP>(aw_next, al, f.stride, f.t0, rev ? t - 1 : t + 1, nqp);
             }
             if (many == 0ull) continue;  // wave-uniform: nothing live (FILT: and allowed for a query of the pass) in this tile
-            const float4 *rp = data + (size_t)t * NC * 64 + lane;
+            const float4 *rp = data + (size_t)t * (D ? NC : (int)(a.dim >> 2)) * 64 + lane;
             if constexpr (WHOLE) {
                 float4 xs[NC];
                 if (i >= split) {
@@ -605,7 +623,7 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a, const QSha
                         for (int p = 0; p < 4; p++) acc[j][r][p] = f2v{0.0f, 0.0f};
                 const bool dflt = i >= split;
 #pragma unroll 2
-                for (int b = 0; b < D / 32; b++) {
+                for (int b = 0; b < (D ? D / 32 : nb); b++) {
                     float4 xs[8];
                     if (dflt) {
 #pragma unroll
@@ -620,10 +638,40 @@ __device__ __forceinline__ void qshare_scan_body(const QShareArgs &a, const QSha
                         for (int cc = 0; cc < 8; cc++)
                             chunk_update2<METRIC>(acc[j], cc, qj[j][b * 8 + cc], xs[cc]);
                 }
+                float sum[QP];
+#pragma unroll
+                for (int j = 0; j < QP; j++) sum[j] = 0.0f;
+                if constexpr (D == 0) {
+                    // The rest of the AVX2 order (row_dot_or_l2_generic): each leftover 8-float block goes
+                    // into accumulator row 0 (chunk positions 0 and 1), then four last elements one by one
+                    // through scalar_update into the query's sum, which avx256_reduce adds last.
+                    int c = nb * 8;
+                    for (const int c4 = (int)(a.dim >> 2) & ~1; c < c4; c += 2) {
+                        const float4 *p0 = rp + (size_t)c * 64, *p1 = p0 + 64;
+                        const float4 x0 = dflt ? ld_stream<false>(p0) : ld_stream<true>(p0);
+                        const float4 x1 = dflt ? ld_stream<false>(p1) : ld_stream<true>(p1);
+#pragma unroll
+                        for (int j = 0; j < QP; j++) {
+                            chunk_update2<METRIC>(acc[j], 0, qj[j][c], x0);
+                            chunk_update2<METRIC>(acc[j], 1, qj[j][c + 1], x1);
+                        }
+                    }
+                    if (a.dim & 4u) {  // wave-uniform
+                        const float4 x = dflt ? ld_stream<false>(rp + (size_t)c * 64) : ld_stream<true>(rp + (size_t)c * 64);
+#pragma unroll
+                        for (int j = 0; j < QP; j++) {
+                            const f4v q = qj[j][c];
+                            scalar_update<METRIC>(sum[j], q.x, x.x);
+                            scalar_update<METRIC>(sum[j], q.y, x.y);
+                            scalar_update<METRIC>(sum[j], q.z, x.z);
+                            scalar_update<METRIC>(sum[j], q.w, x.w);
+                        }
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < QP; j++)
                     if ((uint32_t)j < nqp)
-                        tk[j].offer_bounded(lane_key(FILT ? mq[FILT ? j : 0] : m, wrap_metric(a.metric, avx256_reduce2(acc[j])), t, lane),
+                        tk[j].offer_bounded(lane_key(FILT ? mq[FILT ? j : 0] : m, wrap_metric(a.metric, avx256_reduce2(acc[j], sum[j])), t, lane),
                                             [&] { return seed_bound(sd + j); });
             }
         }
@@ -670,6 +718,22 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
     qshare_scan_body<METRIC, D, E, WHOLE, false, true>(a, f);
 }
 
+// The runtime-dimension block form (D = 0: every dimension qshare_supported admits but 128 and 768):
+// a.dim >> 5 blocks, then the tail of the AVX2 order; 4 queries per pass, 2 at E = 4.
+template <int METRIC, int E>
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_dyn_kernel(
+    QShareArgs a)
+{
+    qshare_scan_body<METRIC, 0, E, false, false, false>(a, QShareFilt{});
+}
+
+template <int METRIC, int E>
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_dyn_filt_kernel(
+    QShareArgs a, QShareFilt f)
+{
+    qshare_scan_body<METRIC, 0, E, false, false, true>(a, f);
+}
+
 // The screened form: L2, d = 128, k <= 64, whole rows.
 __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_screen_kernel(
     QShareArgs a)
@@ -684,10 +748,21 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
 }
 
 // Which corpora the kernel covers, its queries per pass and its grid.
+// (dim % 4: device search's own condition.  dim = 4 stays out: below 8 elements the reference returns the
+// scalar sum without the reduction tree, and a -0.0 sum would differ.)
 bool qshare_supported(int metric, uint32_t dim, int order512)
 {
-    return (metric == WVG_M_L2 || metric == WVG_M_DOT || metric == WVG_M_COSINE) && (dim == 128 || dim == 768) &&
+    return (metric == WVG_M_L2 || metric == WVG_M_DOT || metric == WVG_M_COSINE) && dim % 4 == 0 && dim >= 8 &&
            !order512;
+}
+
+// The kernels' D of a corpus: 128 and 768 have fixed forms, 0 = the runtime-dimension form.
+static int qshare_fixed_dim(uint32_t dim)
+{
+#ifdef WVG_TOOLS
+    if (tuning().qshare == 3) return 0;  // A/B: the runtime-dimension form at d = 128 and 768 too
+#endif
+    return dim == 128 || dim == 768 ? (int)dim : 0;
 }
 
 static bool qshare_whole(uint32_t dim)
@@ -695,13 +770,13 @@ static bool qshare_whole(uint32_t dim)
 #ifdef WVG_TOOLS
     if (tuning().qshare == 2) return false;  // A/B: the block shape at d = 128 too
 #endif
-    return dim == 128;
+    return qshare_fixed_dim(dim) == 128;
 }
 
 uint32_t qshare_queries_per_pass(uint32_t dim, uint32_t k)
 {
     const int e = k <= 64 ? 1 : (k <= 128 ? 2 : 4);
-    return (uint32_t)qshare_qp((int)dim, e, qshare_whole(dim));
+    return (uint32_t)qshare_qp(qshare_fixed_dim(dim), e, qshare_whole(dim));
 }
 
 // Two 4-wave workgroups per CU (the kernels stay within 256 registers), every wave at least one tile.
@@ -737,7 +812,11 @@ template <int METRIC, int E>
 static hipError_t launch_seed_e(const QShareArgs &a, hipStream_t s, const QShareFilt *f)
 {
     dim3 grid(a.nq), block(SEED_WAVES * 64);
-    if (a.dim != 128 && a.dim != 768) return hipErrorInvalidValue;
+    if (a.dim != 128 && a.dim != 768) {  // no sample and no screen at the other dimensions
+        if (a.seed_tiles || a.screen) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(qshare_open_seed_kernel, grid, block, 0, s, a);
+        return hipGetLastError();
+    }
     if (f) {
         if (a.dim == 128)
             hipLaunchKernelGGL((qshare_seed_filt_kernel<METRIC, 128, E>), grid, block, 0, s, a, *f);
@@ -773,6 +852,13 @@ static hipError_t launch_qshare_e(const QShareArgs &a, uint32_t mergers, hipStre
             launch_timed(scan_f32_qshare_screen_filt_kernel, grid, block, 0, s, a, *f);
         else
             launch_timed(scan_f32_qshare_screen_kernel, grid, block, 0, s, a);
+        return hipGetLastError();
+    }
+    if (qshare_fixed_dim(a.dim) == 0) {  // the runtime-dimension form
+        if (f)
+            launch_timed((scan_f32_qshare_dyn_filt_kernel<METRIC, E>), grid, block, 0, s, a, *f);
+        else
+            launch_timed((scan_f32_qshare_dyn_kernel<METRIC, E>), grid, block, 0, s, a);
         return hipGetLastError();
     }
     if (f) {  // the filtered forms: whole rows at d = 128, blocks at d = 768

@@ -1318,6 +1318,36 @@ static bool qshare_route(const wvg_corpus *c, uint32_t nq)
            qshare_supported(c->metric, c->dim, c->ctx->order512);
 }
 
+// What a pipelined call of nq queries over the tiles of p1 does: search_pipelined routes by it and
+// wvg_search_device_pipelined_plan reports it.  seed_tiles: the prologue's sample (QShareArgs).
+static wvg_stream_plan stream_plan(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k, uint32_t *seed_tiles)
+{
+    wvg_stream_plan sp{0u, 1u, p1.empty ? 0u : nq, 0u, 0u};
+    *seed_tiles = 0;
+    if (p1.empty || tuning().pipeline_mode != 1 || !qshare_route(c, nq)) return sp;
+    sp.shared_rows = 1;
+    sp.queries_per_pass = qshare_queries_per_pass(c->dim, k);
+    sp.passes = (nq + sp.queries_per_pass - 1) / sp.queries_per_pass;
+    *seed_tiles = qshare_seed_tiles(c->dim, p1.te - p1.tb, qshare_groups(p1.te - p1.tb, c->ctx->num_cus));
+    sp.seeded = *seed_tiles > 0;
+    sp.screened = c->ctx->qshare_screen && qshare_screened(c->metric, c->dim, k, *seed_tiles);
+    return sp;
+}
+
+int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg_stream_plan *out)
+{
+    if (!c || !out) return fail(WVG_ERR_INVALID, "null corpus / plan");
+    if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "k above 256 is not supported by the fused top-k");
+    if (c->kind != WVG_KIND_F32) return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32 corpora");
+    if (c->dim % 4 != 0) return fail(WVG_ERR_UNSUPPORTED, "device search needs dim % 4 == 0");
+    *out = wvg_stream_plan{0u, 1u, 0u, 0u, 0u};
+    if (nq == 0 || k == 0) return WVG_OK;
+    std::shared_lock<std::shared_mutex> lk(c->rw);
+    uint32_t seed_tiles;
+    *out = stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k, &seed_tiles);
+    return WVG_OK;
+}
+
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
 {
     if (!c) return 0;
@@ -1400,7 +1430,9 @@ static int search_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, 
         WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));  // wvg_search's write_empty
         return WVG_OK;
     }
-    if (tuning().pipeline_mode == 1 && qshare_route(c, nq)) {  // shared rows: one launch, rows read once per pass
+    uint32_t seed_tiles;
+    const wvg_stream_plan sp = stream_plan(c, p, nq, k, &seed_tiles);
+    if (sp.shared_rows) {  // shared rows: one launch, rows read once per pass
         const QShareLayout l = qshare_layout(c, p, nq, k);
         if (!d_workspace || workspace_bytes < l.total) return fail(WVG_ERR_INVALID, "workspace too small");
         char *w = (char *)d_workspace;
@@ -1424,16 +1456,15 @@ static int search_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, 
         a.nq = nq;
         a.k = k;
         a.groups = l.groups;
-        const uint32_t qp = qshare_queries_per_pass(c->dim, k);
-        a.reverse = next_direction(c, (nq + qp - 1) / qp);  // one direction per pass
+        a.reverse = next_direction(c, sp.passes);  // one direction per pass
         a.plain = plain_loads(c, p.tb, p.te);
         a.cache_tail256 = k1_cache_tail(c, p.tb, p.te);
         a.metric = c->metric;
         const uint32_t mergers = tuning().qshare_mergers > 0 ? (uint32_t)tuning().qshare_mergers : std::min<uint32_t>(nq, 64);
         a.seeds = (uint64_t *)(w + l.seeds);
-        a.seed_tiles = qshare_seed_tiles(c->dim, p.te - p.tb, l.groups);
+        a.seed_tiles = seed_tiles;
         a.seq_combine = tuning().qshare_combine == 0;
-        a.screen = c->ctx->qshare_screen && qshare_screened(c->metric, c->dim, k, a.seed_tiles);
+        a.screen = sp.screened;
         if (a.screen) {
             a.qbf = (uint16_t *)(w + l.qbf);
             a.qconst = (float4 *)(w + l.qconst);

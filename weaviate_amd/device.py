@@ -13,7 +13,7 @@ from ctypes import byref, c_int, c_uint64, c_void_p
 import numpy as np
 
 from . import _lib
-from ._lib import check, fptr, u32ptr, u64ptr
+from ._lib import StreamPlan, check, fptr, u32ptr, u64ptr
 
 
 def device_count() -> int:
@@ -248,6 +248,13 @@ class Corpus:
             check(self.lib.wvg_search_device_pipelined_filtered(self.handle, d_queries, nq, k, d_allow, allow_stride,
                                                                 allow_first_id, d_ids, d_dists, d_counts, d_workspace,
                                                                 workspace_bytes, stream))
+
+    def search_device_plan(self, nq: int, k: int) -> dict:
+        """wvg_search_device_pipelined_plan: what search_device_pipelined(nq, k) will do on this corpus --
+        {shared_rows, queries_per_pass, passes, seeded, screened} (struct wvg_stream_plan).  Host only."""
+        sp = StreamPlan()
+        check(self.lib.wvg_search_device_pipelined_plan(self.handle, nq, k, byref(sp)))
+        return {name: int(getattr(sp, name)) for name, _ in StreamPlan._fields_}
 
     def search_by_distance(self, query, target: float, max_limit: int = -1, allow=None, capacity: int | None = None):
         """wvg_search_by_distance: (ids, dists) of every row within `target`

@@ -321,7 +321,11 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * under capture that never happens -- a corpus without a current shadow takes
  * the exact path, one with a shadow waits for it before the capture (run one
  * uncaptured batch first to warm it).  d_counts may be NULL.  One workspace
- * serves any number of calls issued in order on one stream.  An empty corpus
+ * serves any number of calls issued in order on one stream.  Its first 256
+ * bytes are a status block that is the same for every entry point, (nq, k)
+ * and corpus: the sticky status word wvg_search_device_check reads, and the
+ * arrival counter of wvg_search_device_pipelined's prologue, which is zero
+ * between calls -- the one zero fill is what starts it.  An empty corpus
  * (e.g. a rank whose slab holds no rows) yields empty results: ids
  * UINT64_MAX, dists +inf, counts 0 (as wvg_search).  wvg_search_device
  * takes F32, BQ and PQ corpora (d_queries: float [nq][dim]; BQ codes and PQ
@@ -344,7 +348,9 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
  * scan's part of the workspace (its hand-off words and, where every wave
  * scans only a few tiles, per query the k-th distance of a sample of the
  * first rows, which bounds the scan's lists from the start; the results do
- * not depend on it).  Everywhere else (one query, other metrics, d = 4, the
+ * not depend on it).  In the prologue one wave scores one (sample tile,
+ * query) pair anywhere on the chip and the workgroup that finishes last
+ * combines them; no workgroup waits for another.  Everywhere else (one query, other metrics, d = 4, the
  * AVX-512 order, cache_reuse = 0) every query is one full scan of the corpus:
  * the scan workgroups walk the queries back to back and one extra workgroup
  * merges each query's lists while the scan moves on.  F32 corpora; same

@@ -589,6 +589,9 @@ int wvgx_set_tuning(int key, int value)
     } else if (key == 40) {
         old = t.qshare_screen;
         t.qshare_screen = value;
+    } else if (key == 41 && value >= 1) {
+        old = t.qshare_seed_share;
+        t.qshare_seed_share = value;
     }
     return old;
 }

@@ -345,6 +345,9 @@ hipError_t launch_scan_f32_stream(const ScanArgs &a, const StreamJob &j, hipStre
 // the ready words and writes seeds[q]: the k-th smallest key of query q over the
 // first seed_tiles tiles of [tile_begin, tile_end), scored with the scan's own
 // chain (KEY_NONE with fewer than k live rows there, or with seed_tiles = 0).
+// One wave scores one (sample tile, query) pair and publishes its sorted keys to
+// QSharePro::lists; the workgroup that arrives last at a counter of QSharePro::arrivals merges
+// its queries' lists and resets the counter, no workgroup waits (wvg_qshare.hip).
 // The sample is part of the scanned rows, so its k-th key is an upper bound of
 // the result's k-th key: the scan's lists start with tau = seed + 1 and a wave
 // sorts or inserts only the rows at or below the seed key, not the first k it
@@ -384,6 +387,15 @@ struct QShareArgs {
                              // half) and all (query, tile) pairs (high half); [1] admitted (query, row) pairs (low
                              // half) and rounds of the exact chain (high half)
 };
+// The prologue's own hand-off, a second argument of qshare_seed_kernel / qshare_seed_filt_kernel (the scan
+// kernels' arguments and code stay as they are).
+constexpr uint32_t PRO_COUNTERS = 16;
+struct QSharePro {
+    uint64_t *lists;     // [nq][seed_tiles][min(k, 64)] each (query, sample tile) pair's sorted keys
+    uint32_t *arrivals;  // [PRO_COUNTERS] arrival counters, counter c for the blocks of 8 queries c, c + 16, ...:
+                         // words of the workspace's status block, zero between calls (the workgroup that
+                         // arrives last at a counter puts it back)
+};
 // Per-query allow lists of a shared-row launch (wvg_search_device_pipelined_filtered): the filtered
 // kernels (scan_f32_qshare_filt_kernel, scan_f32_qshare_screen_filt_kernel, qshare_seed_filt_kernel) take
 // this beside QShareArgs, so the unfiltered kernels and their arguments stay as they are.  Query q's word
@@ -409,7 +421,7 @@ uint32_t qshare_groups(uint64_t ntiles, int num_cus);
 // Tiles of the prologue's sample for a scan of ntiles tiles by `groups` workgroups (0 = no seeding).
 uint32_t qshare_seed_tiles(uint32_t dim, uint64_t ntiles, uint32_t groups);
 // f: null = the unfiltered kernels; otherwise the filtered ones.
-hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s, const QShareFilt *f = nullptr);
+hipError_t launch_qshare_seed(const QShareArgs &a, const QSharePro &pro, hipStream_t s, const QShareFilt *f = nullptr);
 hipError_t launch_scan_f32_qshare(const QShareArgs &a, uint32_t mergers, hipStream_t s, const QShareFilt *f = nullptr);
 // Grouped search (wvg_search_group, wvg_group.hip): nq single-query scans, query i
 // over a corpus of its own, as ONE scan launch and one merge launch.  The host
@@ -635,10 +647,17 @@ struct Tuning {
                              // d = 128 and 768 too (A/B against their fixed forms)
     int qshare_mergers = 0;  // its merge workgroups (tuning key 35): 0 = one per query (at most 64), n = n (1 = the
                              // queries merged one after another; A/B)
-    int qshare_seed = 32;    // shared-row scan (tuning key 37): tiles of the prologue's row sample whose k-th key
-                             // bounds every wave's list from the start; 0 = no seeding (A/B).  1M x 128, 16 queries:
-                             // 16 / 32 / 64 / 128 tiles -> 83.7k / 84.2k / 82.2k / 75.4k QPS, 64.8k without
-                             // (profiles/r11/qshare_seed/: the prologue costs ~0.3 us per tile)
+    int qshare_seed = 64;    // shared-row scan (tuning key 37): tiles of the prologue's row sample whose k-th key
+                             // bounds every wave's list from the start; 0 = no seeding (A/B).  1M x 128, 16 queries,
+                             // tools build, 32 / 64 / 128 / 256 / 512 tiles: 111.3k / 113.2k / 110.8k / 102.9k /
+                             // 93.9k QPS, prologue 10.5 / 11.4 / 15.8 / 28.1 / 46.5 us, scan 128.6 / 125.8 / 124.9 /
+                             // 120.8 / 122.5 us: up to 128 tiles x 16 queries every pair has a wave of its own on the
+                             // chip, beyond that the pairs queue (profiles/r17/qshare_prologue/)
+    int qshare_seed_share = 64;  // (tuning key 41) the sample grows past 32 tiles only up to 1 / this of the range
+                                 // (qshare_seed_tiles), so that a mid-size corpus is not searched twice: 100k rows
+                                 // (1,563 tiles) with 128 / 97 / 32 sample tiles ran 210.5k / 215.0k / 221.3k QPS,
+                                 // so the sample passes 32 tiles only above 2,048 tiles and reaches 64 at 4,096;
+                                 // 8M rows: 32 / 128 / 256 tiles 22.98k / 23.08k / 22.87k QPS
     int qshare_seed_tpw = 124;  // (tuning key 38) seed only while a wave scans at most this many tiles,
                                 // ntiles / (groups x SCAN_WAVES): the saving is a fixed ~80-110 us per launch
                                 // (+29 % at 8, +10 % at 30, +4 % at 122 tiles per wave, the largest measured)

@@ -223,13 +223,34 @@ __device__ __forceinline__ void screen_query_side(const QShareArgs &a, uint32_t 
 }
 
 // The prologue of a shared-row launch.  The grid zeroes the ready words; then
-// workgroup q scores the first a.seed_tiles tiles of the range for query q -- a
-// wave the tiles wave, wave + SEED_WAVES, ..., with the scan's validity words
-// and the scan's chain (chunk_update2 in chunk order, avx256_reduce2,
-// wrap_metric, lane_key: the keys are the scan's bit for bit) -- and writes the
-// sample's k-th smallest key to seeds[q], KEY_NONE with fewer than k live rows.
-// FILT: query q's sample is the rows of valid & allow_q (QShareFilt).
-constexpr int SEED_WAVES = 16;
+// one WAVE scores one (sample tile, query) pair: workgroup b holds tile b % T of
+// the first T = a.seed_tiles tiles of the range and the queries PRO_WAVES (b / T)
+// + wave, so the queries of a tile meet in one workgroup and the tile comes from
+// HBM once (T % 8 == 0 puts the workgroups of one tile on one XCD's L2).  The
+// wave loads its whole tile at once -- behind no mask, allow word or query: a
+// tile of the range is memory whatever its mask says -- runs the scan's chain
+// (chunk_update2 in chunk order, avx256_reduce2, wrap_metric, lane_key with the
+// scan's validity word: the keys are the scan's bit for bit), sorts its 64 keys
+// and publishes the first min(k, 64) of them to pro.lists[q][tile] in the
+// hand-off form of pass_combine_publish (agent-scope stores, the storing wave's
+// drain); after the workgroup's barrier one agent-scope add tells the
+// workgroup's arrival at pro.arrivals[c], c = its query block mod PRO_COUNTERS.
+// A pair with an empty mask (a dead tile, an allow word of zero, a tile past the
+// range, FILT: query q's sample is the rows of valid & allow_q) publishes
+// KEY_NONE throughout and arrives like any other.  Nobody waits: the workgroup
+// that arrives last at counter c -- its add returns T x (query blocks of class c)
+// - 1 -- puts the counter back to zero for the next call and merges the queries
+// of class c's blocks, wave w the w-th query of each (up to 128 queries: every
+// wave one query, PRO_COUNTERS workgroups merging side by side), a lane per list
+// as merge_lists_body reads them (agent-scope loads, as merge_lists_ready; up to
+// PRO_CHUNK keys per lane in flight, since a dependent load per key was most of
+// the merge's time), and writes seeds[q]: the sample's k-th smallest key,
+// KEY_NONE with fewer than k live rows.  Every other workgroup exits.  The
+// counters lie in the workspace's status block (QSharePro).
+// Without a sample (seed_tiles = 0, d = 768) T = 1 and every seed is opened.
+constexpr int SEED_WAVES = 16;  // qshare_open_seed_kernel's workgroup
+constexpr int PRO_WAVES = 8;    // two waves per SIMD: 256 registers, the tile's 128 and the chain beside them
+constexpr int PRO_CHUNK = 12;   // keys of a list a merging lane loads at once (48 KiB of LDS for the workgroup)
 
 // Query q's allow word of tile t: wave-uniform, and no word outside [0, stride) is read.
 __device__ __forceinline__ uint64_t allow_word(cu64 *aq, uint64_t stride, uint64_t t0, uint64_t t)
@@ -239,69 +260,132 @@ __device__ __forceinline__ uint64_t allow_word(cu64 *aq, uint64_t stride, uint64
 }
 
 template <int METRIC, int D, int E, bool FILT>
-__device__ __forceinline__ void qshare_seed_body(const QShareArgs &a, const QShareFilt &f, uint32_t bdim, uint32_t gdim)
+__device__ __forceinline__ void qshare_seed_body(const QShareArgs &a, const QSharePro &pro, const QShareFilt &f,
+                                                 uint32_t bdim, uint32_t gdim)
 {
     static_assert(D % 32 == 0 && D > 0 && !is_abs_or_neq<METRIC>, "shared rows: fixed D, the AVX2 chains");
     constexpr int NC = D / 4;
+    constexpr bool WHOLE = D <= 128;  // the tile in registers at once; larger rows in blocks of 32 floats
     const uint64_t nready = (uint64_t)a.nq * a.groups;
     for (uint64_t i = (uint64_t)blockIdx.x * bdim + threadIdx.x; i < nready; i += (uint64_t)gdim * bdim)
         a.ready[i] = 0u;
-    const uint32_t q = blockIdx.x;  // gridDim.x == nq
     const int lane = threadIdx.x & 63, wave = wave_id();
-    cf4 *qj = (cf4 *)a.queries + (size_t)q * (a.qpitch / 4);
-    if constexpr (METRIC == WVG_M_L2 && D == QS_D) {
-        if (a.screen) {  // the scan screens: its query side, by the last wave (it has the fewest sample tiles)
-#ifdef WVG_TOOLS
-            if (threadIdx.x == 0 && q == 0) a.screen_count[0] = a.screen_count[1] = 0ull;
-#endif
-            if (wave == SEED_WAVES - 1) screen_query_side(a, q, qj, lane);
-        }
-    }
+    const uint32_t T = a.seed_tiles ? a.seed_tiles : 1u;  // gridDim.x == T * ceil(nq / PRO_WAVES)
+    const uint32_t ti = blockIdx.x % T, q = blockIdx.x / T * PRO_WAVES + (uint32_t)wave;
+    const bool hasq = q < a.nq;  // wave-uniform
     const uint64_t ntiles = a.tile_end - a.tile_begin;
     const uint64_t ns = a.seed_tiles < ntiles ? a.seed_tiles : ntiles;
-    if (ns == 0) {  // workgroup-uniform
-        if (threadIdx.x == 0) a.seeds[q] = WVG_KEY_NONE;
+    const uint64_t t = a.tile_begin + ti;
+    const bool score = hasq && ti < ns;  // wave-uniform
+    cf4 *qj = (cf4 *)a.queries + (size_t)(hasq ? q : 0u) * (a.qpitch / 4);
+    const float4 *rp = reinterpret_cast<const float4 *>(a.data) + (size_t)t * NC * 64 + lane;
+    float4 xs[WHOLE ? NC : 1];
+    if constexpr (WHOLE) {
+        if (score) {  // default policy: the scan reads them again
+#pragma unroll
+            for (int c = 0; c < NC; c++) xs[c] = rp[(size_t)c * 64];
+        }
+    }
+    if constexpr (METRIC == WVG_M_L2 && D == QS_D) {
+        if (a.screen) {  // the scan screens: its query side, by the query's wave of tile 0, under the row loads
+#ifdef WVG_TOOLS
+            if (threadIdx.x == 0 && blockIdx.x == 0) a.screen_count[0] = a.screen_count[1] = 0ull;
+#endif
+            if (ti == 0 && hasq) screen_query_side(a, q, qj, lane);
+        }
+    }
+    if (ns == 0) {  // grid-uniform: no sample, every seed open
+        if (hasq && lane == 0) a.seeds[q] = WVG_KEY_NONE;
         return;
     }
-    const float4 *data = reinterpret_cast<const float4 *>(a.data);
-    cu64 *valid = (cu64 *)a.valid;
-    cu64 *aq = FILT ? (cu64 *)f.allow + (size_t)q * f.stride : nullptr;
-    WaveTopK<E> tk;
-    tk.init((int)a.k);
-    for (uint64_t t = a.tile_begin + (uint64_t)wave; t < a.tile_begin + ns; t += SEED_WAVES) {
-        uint64_t m = valid[t];
-        if constexpr (FILT) m &= allow_word(aq, f.stride, f.t0, t);
-        if (m == 0ull) continue;  // wave-uniform
-        const float4 *rp = data + (size_t)t * NC * 64 + lane;
-        f2v acc[4][4];
+    uint64_t key = WVG_KEY_NONE;
+    if (score) {
+        uint64_t m = ((cu64 *)a.valid)[t];
+        if constexpr (FILT) m &= allow_word((cu64 *)f.allow + (size_t)q * f.stride, f.stride, f.t0, t);
+        if (m != 0ull) {  // wave-uniform
+            f2v acc[4][4];
 #pragma unroll
-        for (int r = 0; r < 4; r++)
+            for (int r = 0; r < 4; r++)
 #pragma unroll
-            for (int p = 0; p < 4; p++) acc[r][p] = f2v{0.0f, 0.0f};
+                for (int p = 0; p < 4; p++) acc[r][p] = f2v{0.0f, 0.0f};
+            if constexpr (WHOLE) {
+#pragma unroll
+                for (int c = 0; c < NC; c++) chunk_update2<METRIC>(acc, c & 7, qj[c], xs[c]);
+            } else {
 #pragma unroll 2
-        for (int b = 0; b < D / 32; b++) {
-            float4 xs[8];
+                for (int b = 0; b < D / 32; b++) {
+                    float4 xb[8];
 #pragma unroll
-            for (int cc = 0; cc < 8; cc++) xs[cc] = rp[(size_t)(b * 8 + cc) * 64];  // default policy: the scan reads them again
+                    for (int cc = 0; cc < 8; cc++) xb[cc] = rp[(size_t)(b * 8 + cc) * 64];
 #pragma unroll
-            for (int cc = 0; cc < 8; cc++) chunk_update2<METRIC>(acc, cc, qj[b * 8 + cc], xs[cc]);
+                    for (int cc = 0; cc < 8; cc++) chunk_update2<METRIC>(acc, cc, qj[b * 8 + cc], xb[cc]);
+                }
+            }
+            key = lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane);
+            sort64(key);
         }
-        tk.offer(lane_key(m, wrap_metric(a.metric, avx256_reduce2(acc)), t, lane));
     }
-    const uint64_t kth = group_combine_kth<E, SEED_WAVES>(tk);
-    if (threadIdx.x == 0) a.seeds[q] = kth;
+    const uint32_t kk = a.k < 64u ? a.k : 64u;  // a tile holds 64 keys
+    if (hasq && (uint32_t)lane < kk)
+        __hip_atomic_store((gu64 *)(pro.lists + ((size_t)q * T + ti) * kk + lane), key, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its own list
+    __shared__ uint32_t last_sh;
+    __shared__ uint64_t stage[PRO_WAVES][PRO_CHUNK][64];  // the merge's keys, lane by lane
+    __syncthreads();
+    const uint32_t nqb = (a.nq + PRO_WAVES - 1) / PRO_WAVES, qb = blockIdx.x / T, cls = qb % PRO_COUNTERS;
+    gu32 *ctr = (gu32 *)pro.arrivals + cls;
+    if (threadIdx.x == 0) {  // class cls: the query blocks cls, cls + PRO_COUNTERS, ... with T workgroups each
+        const uint32_t want = T * ((nqb - cls + PRO_COUNTERS - 1) / PRO_COUNTERS);
+        last_sh = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == want - 1u;
+    }
+    __syncthreads();
+    if (!last_sh) return;  // workgroup-uniform: only the class's last arriver goes on, and it waits for nobody
+    if (threadIdx.x == 0) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint32_t mq = cls * PRO_WAVES + (uint32_t)wave; mq < a.nq; mq += PRO_COUNTERS * PRO_WAVES) {
+        WaveTopK<E> tk;
+        tk.init((int)a.k);
+        for (uint32_t g0 = 0; g0 < T; g0 += 64) {
+            const uint32_t list = g0 + lane;
+            const bool have = list < T;
+            const gu64 *lp = (const gu64 *)(pro.lists + ((size_t)mq * T + (have ? list : 0u)) * kk);
+            for (uint32_t r0 = 0; r0 < kk; r0 += PRO_CHUNK) {
+                uint64_t c[PRO_CHUNK];
+#pragma unroll
+                for (int i = 0; i < PRO_CHUNK; i++)
+                    c[i] = have && r0 + i < kk ? __hip_atomic_load(lp + r0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                               : WVG_KEY_NONE;
+                // through LDS (the lane's own words): one rolled loop offers them, tk's code stands once
+#pragma unroll
+                for (int i = 0; i < PRO_CHUNK; i++) stage[wave][i][lane] = c[i];
+                const uint32_t n = kk - r0 < (uint32_t)PRO_CHUNK ? kk - r0 : (uint32_t)PRO_CHUNK;
+                bool stop = false;
+#pragma unroll 1
+                for (uint32_t i = 0; i < n; i++) {
+                    const uint64_t key = stage[wave][i][lane];
+                    if (r0 + i > 0 && __ballot(key < tk.tau) == 0ull) {  // sorted lists: the rest cannot enter
+                        stop = true;
+                        break;
+                    }
+                    tk.offer(key);
+                }
+                if (stop) break;
+            }
+        }
+        if (lane == 0) a.seeds[mq] = tk.tau;  // element k - 1, KEY_NONE while the list is not full
+    }
 }
 
 template <int METRIC, int D, int E>
-__global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_kernel(QShareArgs a)
+__global__ __launch_bounds__(PRO_WAVES * 64) void qshare_seed_kernel(QShareArgs a, QSharePro pro)
 {
-    qshare_seed_body<METRIC, D, E, false>(a, QShareFilt{}, blockDim.x, gridDim.x);  // (read in the kernel: the code of before)
+    qshare_seed_body<METRIC, D, E, false>(a, pro, QShareFilt{}, blockDim.x, gridDim.x);
 }
 
 template <int METRIC, int D, int E>
-__global__ __launch_bounds__(SEED_WAVES * 64) void qshare_seed_filt_kernel(QShareArgs a, QShareFilt f)
+__global__ __launch_bounds__(PRO_WAVES * 64) void qshare_seed_filt_kernel(QShareArgs a, QSharePro pro, QShareFilt f)
 {
-    qshare_seed_body<METRIC, D, E, true>(a, f, blockDim.x, gridDim.x);
+    qshare_seed_body<METRIC, D, E, true>(a, pro, f, blockDim.x, gridDim.x);
 }
 
 // The prologue without a sample (the runtime-dimension form runs unseeded): the
@@ -791,12 +875,17 @@ uint32_t qshare_groups(uint64_t ntiles, int num_cus)
 // scan is bound by the VALU: at d = 768 a pass is bound by HBM, the start-up
 // hides under the loads and the sample costs 6x the reads (1M x 768, 16
 // queries: launch 1789 -> 1799 us, prologue 145 us), so only d = 128 is seeded.
+constexpr uint64_t QSHARE_SEED_FLOOR = 32;
 uint32_t qshare_seed_tiles(uint32_t dim, uint64_t ntiles, uint32_t groups)
 {
     const Tuning &t = tuning();
     if (t.qshare_seed <= 0 || dim != 128 || groups == 0) return 0;
     if (ntiles / ((uint64_t)groups * SCAN_WAVES) > (uint64_t)t.qshare_seed_tpw) return 0;
-    return (uint32_t)std::min<uint64_t>((uint64_t)t.qshare_seed, ntiles);
+    // Every sample tile has a wave of its own, so the prologue's time hardly grows with the sample; its reads
+    // do.  Up to QSHARE_SEED_FLOOR tiles are sampled whatever the range (the sample of before); beyond that
+    // the sample stays within 1 / qshare_seed_share of the range.
+    const uint64_t share = std::max<uint64_t>(QSHARE_SEED_FLOOR, ntiles / (uint64_t)std::max(t.qshare_seed_share, 1));
+    return (uint32_t)std::min({(uint64_t)t.qshare_seed, share, ntiles});
 }
 
 // The screened form runs where seeding runs, for L2 with k <= 64 and whole rows:
@@ -809,35 +898,39 @@ bool qshare_screened(int metric, uint32_t dim, uint32_t k, uint32_t seed_tiles)
 }
 
 template <int METRIC, int E>
-static hipError_t launch_seed_e(const QShareArgs &a, hipStream_t s, const QShareFilt *f)
+static hipError_t launch_seed_e(const QShareArgs &a, const QSharePro &pro, hipStream_t s, const QShareFilt *f)
 {
-    dim3 grid(a.nq), block(SEED_WAVES * 64);
     if (a.dim != 128 && a.dim != 768) {  // no sample and no screen at the other dimensions
         if (a.seed_tiles || a.screen) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(qshare_open_seed_kernel, grid, block, 0, s, a);
+        hipLaunchKernelGGL(qshare_open_seed_kernel, dim3(a.nq), dim3(SEED_WAVES * 64), 0, s, a);
         return hipGetLastError();
     }
+    if (a.seed_tiles && (!pro.lists || !pro.arrivals)) return hipErrorInvalidValue;
+    // a workgroup per sample tile and block of PRO_WAVES queries (one block of queries without a sample)
+    const uint64_t nwg = (uint64_t)(a.seed_tiles ? a.seed_tiles : 1u) * ((a.nq + PRO_WAVES - 1) / PRO_WAVES);
+    if (nwg > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    dim3 grid((uint32_t)nwg), block(PRO_WAVES * 64);
     if (f) {
         if (a.dim == 128)
-            hipLaunchKernelGGL((qshare_seed_filt_kernel<METRIC, 128, E>), grid, block, 0, s, a, *f);
+            hipLaunchKernelGGL((qshare_seed_filt_kernel<METRIC, 128, E>), grid, block, 0, s, a, pro, *f);
         else
-            hipLaunchKernelGGL((qshare_seed_filt_kernel<METRIC, 768, E>), grid, block, 0, s, a, *f);
+            hipLaunchKernelGGL((qshare_seed_filt_kernel<METRIC, 768, E>), grid, block, 0, s, a, pro, *f);
     } else if (a.dim == 128) {
-        hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 128, E>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 128, E>), grid, block, 0, s, a, pro);
     } else {
-        hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 768, E>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((qshare_seed_kernel<METRIC, 768, E>), grid, block, 0, s, a, pro);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_qshare_seed(const QShareArgs &a, hipStream_t s, const QShareFilt *f)
+hipError_t launch_qshare_seed(const QShareArgs &a, const QSharePro &pro, hipStream_t s, const QShareFilt *f)
 {
     if (!qshare_supported(a.metric, a.dim, 0) || a.nq == 0) return hipErrorInvalidValue;
     auto go = [&](auto M) -> hipError_t {
         constexpr int MM = decltype(M)::value;
-        if (a.k <= 64) return launch_seed_e<MM, 1>(a, s, f);
-        if (a.k <= 128) return launch_seed_e<MM, 2>(a, s, f);
-        return launch_seed_e<MM, 4>(a, s, f);
+        if (a.k <= 64) return launch_seed_e<MM, 1>(a, pro, s, f);
+        if (a.k <= 128) return launch_seed_e<MM, 2>(a, pro, s, f);
+        return launch_seed_e<MM, 4>(a, pro, s, f);
     };
     return a.metric == WVG_M_L2 ? go(MetricTag<WVG_M_L2>{}) : go(MetricTag<WVG_M_DOT>{});
 }

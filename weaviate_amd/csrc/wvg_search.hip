@@ -1267,7 +1267,17 @@ int wvg_search_bq_candidates(wvg_corpus *bq, const float *queries, uint32_t nq, 
 
 // Device-search workspaces start with a 256-byte status block (the sticky
 // status word read by wvg_search_device_check); the scan workspace follows.
+// The block also holds the PRO_COUNTERS arrival counters of the shared-row prologue
+// (QSharePro::arrivals) at WS_SEED_ARRIVALS: the device, chain, stream and
+// shared-row layouts overlay each other behind the block, and calls of different
+// (nq, k) and entry points follow each other on one workspace, so a counter
+// inside a layout would start from whatever the call before left there.  Here
+// only the prologue writes them, they are zero between calls (the caller's one zero
+// fill, then the last arrivers' resets), and wvg_search_device_check clears the
+// status word's four bytes alone.
 static const size_t WS_STATUS_BYTES = 256;
+static const size_t WS_SEED_ARRIVALS = 128;
+static_assert(WS_SEED_ARRIVALS + PRO_COUNTERS * 4 <= WS_STATUS_BYTES, "the counters lie inside the status block");
 
 // Workspace of the query-stream scan (after the status block): partial lists
 // [nq][groups][k], then the per-query arrival counters and the per-list ready
@@ -1289,10 +1299,11 @@ static StreamLayout stream_layout(const SearchPlan &p1, uint32_t nq, uint32_t k)
 // lists [nq][groups][k], the ready words [nq][groups] (zeroed per call by the
 // prologue launch), then the prologue's seeds [nq] (8 bytes each), the screen's
 // query side -- bf16 images [nq][128] (d = 128 only) and bound constants [nq]
-// (16 bytes each) -- and the tools build's screen counter.
+// (16 bytes each) -- the tools build's screen counter, and the prologue's
+// partial lists [nq][seed_tiles][min(k, 64)] (QSharePro::lists).
 struct QShareLayout {
-    size_t partials = 0, ready = 0, seeds = 0, qbf = 0, qconst = 0, count = 0, total = 0;
-    uint32_t groups = 0;
+    size_t partials = 0, ready = 0, seeds = 0, qbf = 0, qconst = 0, count = 0, lists = 0, total = 0;
+    uint32_t groups = 0, seed_tiles = 0;
 };
 static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k)
 {
@@ -1304,7 +1315,9 @@ static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uin
     l.qbf = l.seeds + align_up((size_t)nq * 8, 256);
     l.qconst = l.qbf + (c->dim == 128 ? align_up((size_t)nq * 128 * 2, 256) : 0);
     l.count = l.qconst + (c->dim == 128 ? align_up((size_t)nq * 16, 256) : 0);
-    l.total = l.count + 256;
+    l.lists = l.count + 256;
+    l.seed_tiles = qshare_seed_tiles(c->dim, p1.te - p1.tb, l.groups);
+    l.total = l.lists + align_up((size_t)nq * l.seed_tiles * std::min<uint32_t>(k, 64) * 8, 256);
     return l;
 }
 
@@ -1470,7 +1483,8 @@ static int search_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, 
             a.qconst = (float4 *)(w + l.qconst);
             a.screen_count = (uint64_t *)(w + l.count);
         }
-        WVG_HIP(launch_qshare_seed(a, s, flt));  // zeroes the ready words, writes the seeds
+        const QSharePro pro{(uint64_t *)(w + l.lists), (uint32_t *)(w + WS_SEED_ARRIVALS)};
+        WVG_HIP(launch_qshare_seed(a, pro, s, flt));  // zeroes the ready words, writes the seeds
         ProfArm arm(c->ctx);
         if (arm.rc) return arm.rc;
         WVG_HIP(launch_scan_f32_qshare(a, mergers, s, flt));

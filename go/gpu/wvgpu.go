@@ -988,6 +988,34 @@ func (x *Corpus) DevicePipelinedPlan(nq, k int) (StreamPlan, error) {
 		Passes: int(sp.passes), Seeded: sp.seeded != 0, Screened: sp.screened != 0}, nil
 }
 
+// BatchPlan tells the route a batch of queries takes on a corpus (struct
+// wvg_batch_plan).  Results are identical on every route.
+type BatchPlan struct {
+	Matrix            bool // scored on the matrix cores
+	Screen            int  // 0 none (exact only), 1 bf16 screen + exact rescore, 2 int8 screen + exact rescore
+	ShadowBytesPerRow int  // what the first such search allocates per row of capacity; 0 if none
+}
+
+// BatchPlan: the route of a Search / SearchDevice batch of nq queries with k
+// results each; sharedAllow: the batch carries one allow list.  Host only:
+// nothing is launched.
+func (x *Corpus) BatchPlan(nq, k int, sharedAllow bool) (BatchPlan, error) {
+	defer pin(x)()
+	if nq < 0 || k < 0 {
+		return BatchPlan{}, errors.New("wvgpu: negative nq or k")
+	}
+	var bp C.wvg_batch_plan
+	sa := C.int(0)
+	if sharedAllow {
+		sa = 1
+	}
+	if e := err(C.wvg_search_batch_plan(x.h, C.uint32_t(nq), C.uint32_t(k), sa, &bp)); e != nil {
+		return BatchPlan{}, e
+	}
+	return BatchPlan{Matrix: bp.matrix != 0, Screen: int(bp.screen),
+		ShadowBytesPerRow: int(bp.shadow_bytes_per_row)}, nil
+}
+
 // DeviceAllow is a window of per-query allow lists in HBM for
 // SearchDevicePipelinedFiltered: Words holds [nq][Stride] uint64 and bit b of
 // word w of query q's row stands for docID FirstID + 64*w + b; docIDs outside

@@ -74,9 +74,10 @@ int wvg_open(int device, wvg_ctx **out);
  * defaults).  Fill with wvg_options_default, change fields, then open.     */
 typedef struct wvg_options {
     uint32_t size;             /* sizeof(wvg_options) (ABI guard; set by wvg_options_default) */
-    uint32_t mfma_min_queries; /* dot / cosine batches of at least this many queries are scored on the
-                                  matrix cores (bf16 screen + exact fp32 rescore, or exact fp32 MFMA);
-                                  smaller ones run one HBM-bound scan per query.  0 = never.  Default 32. */
+    uint32_t mfma_min_queries; /* dot / cosine / l2-squared batches of at least this many queries are scored
+                                  on the matrix cores (bf16 / int8 screen + exact fp32 rescore, or -- dot /
+                                  cosine only -- exact fp32 MFMA); smaller ones run one HBM-bound scan per
+                                  query.  0 = never.  Default 32. */
     int32_t cache_reuse;       /* 1 (default): consecutive scans of a corpus alternate direction and read
                                   the last ~320 MB of each pass with the default cache policy, so the next
                                   scan starts on rows still in the 256 MiB Infinity Cache; the queries of a
@@ -91,6 +92,10 @@ typedef struct wvg_options {
                                   MFMA (d = 512 / 768 / 1024; other d: bf16) and a per-row error bound,
                                   then rescore the candidates exactly in fp32 (results identical to the
                                   exact path); 1: the bf16 screen for every d; 0: exact fp32 MFMA only.
+                                  l2-squared batches (d % 32 == 0, k <= 16): 1 and 2 both mean the bf16
+                                  screen (shadow: 2 * dim + 4 bytes per row, at the first screened
+                                  batch); 0: the co-scheduled per-query scans, as batches of fewer than
+                                  mfma_min_queries.
                                   The first screened search of a corpus allocates its shadow: int8 = dim
                                   + 8 bytes per row of capacity (7.7 GB at 10M x 768; its first build
                                   also takes one pass over the rows for the corpus scale and one host
@@ -316,8 +321,8 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * (a hipStream_t, NULL = default stream); no host synchronization, no
  * allocation (caller supplies a workspace of wvg_search_workspace_size bytes,
  * zero-filled once before its first use), so a call can be captured in a
- * hipGraph.  Exception: the first screened dot / cosine batch of a corpus
- * (batch_screen) allocates and builds the corpus's shadow on `stream`;
+ * hipGraph.  Exception: the first screened batch of a corpus (batch_screen;
+ * dot / cosine / l2-squared) allocates and builds its shadow on `stream`;
  * under capture that never happens -- a corpus without a current shadow takes
  * the exact path, one with a shadow waits for it before the capture (run one
  * uncaptured batch first to warm it).  d_counts may be NULL.  One workspace
@@ -403,6 +408,25 @@ typedef struct wvg_stream_plan {
     uint32_t screened;         /* the bf16 screen runs */
 } wvg_stream_plan;
 int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg_stream_plan *out);
+/* The route a batch of nq queries with this k takes on corpus c (wvg_search,
+ * wvg_search_device, wvg_multi_search), for a caller that sizes its batches
+ * or wants to see the route: results are identical on every route by design.
+ * Host only: nothing launched; computed by the functions the search itself
+ * routes with.  Answers for every kind and metric: F32 dot / cosine /
+ * l2-squared batches of at least mfma_min_queries report matrix = 1 and their
+ * screen (l2-squared: the bf16 screen, 1, where it applies -- d % 32 == 0,
+ * k <= 16, the AVX2 order, batch_screen != 0 -- and no matrix path at all
+ * elsewhere); BQ / PQ corpora, other metrics, smaller batches, k > 256, an
+ * empty corpus, nq == 0 or k == 0: all zero.  shared_allow_list != 0: the
+ * batch carries one allow list for all its queries; the route is the same.
+ * Per-query allow windows never take the matrix path.                      */
+typedef struct wvg_batch_plan {
+    uint32_t matrix;   /* 1: scored on the matrix cores */
+    uint32_t screen;   /* 0 none (exact only), 1 bf16 screen + exact rescore, 2 int8 screen + exact rescore */
+    uint32_t shadow_bytes_per_row; /* what the first such search allocates per row of capacity; 0 if none */
+    uint32_t reserved;
+} wvg_batch_plan;
+int wvg_search_batch_plan(wvg_corpus *c, uint32_t nq, uint32_t k, int shared_allow_list, wvg_batch_plan *out);
 /* Synchronizes `stream` and reads (and clears) the workspace's sticky status
  * word: WVG_ERR_DEVICE if any device search on this workspace since the last
  * check could not complete -- the query-stream merge workgroup of

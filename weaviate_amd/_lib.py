@@ -45,6 +45,12 @@ class StreamPlan(ctypes.Structure):
                 ("seeded", c_uint32), ("screened", c_uint32)]
 
 
+class BatchPlan(ctypes.Structure):
+    """struct wvg_batch_plan (include/wvgpu.h): the route a batch of queries takes on a corpus."""
+    _fields_ = [("matrix", c_uint32), ("screen", c_uint32), ("shadow_bytes_per_row", c_uint32),
+                ("reserved", c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/wvgpu.h.
 _P = POINTER
 SIGNATURES = {
@@ -106,6 +112,7 @@ SIGNATURES = {
                                                      c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                                      c_void_p]),
     "wvg_search_device_pipelined_plan": (c_int, [c_void_p, c_uint32, c_uint32, _P(StreamPlan)]),
+    "wvg_search_batch_plan": (c_int, [c_void_p, c_uint32, c_uint32, c_int, _P(BatchPlan)]),
     "wvg_topk_merge_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "wvg_search_device_check": (c_int, [c_void_p, c_void_p, c_void_p]),

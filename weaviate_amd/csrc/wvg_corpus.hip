@@ -2,7 +2,7 @@
 // (flat.Add / AddBatch / Delete, V/flat/index.go:197-295; the PostStartup
 // bulk load, :640-681), reads by id (vectorById, :401-407), the PQ codebook
 // (NewProductQuantizer validation, CH/product_quantization.go:187-197) and
-// the bf16 shadow state of F32 dot / cosine corpora (K3c / K3d).
+// the bf16 shadow state of F32 dot / cosine / l2-squared corpora (K3c / K3d / K3c-L2).
 
 #include <cstring>
 
@@ -68,7 +68,7 @@ void shadow_free(wvg_corpus *c)
     c->sh_failed = false;  // a failed allocation is retried at the next screened search
 }
 
-// The bf16 shadow (fragments + row norms) of an F32 dot / cosine corpus,
+// The bf16 shadow (fragments + row norms) of an F32 dot / cosine / l2-squared corpus,
 // allocated on first use and rebuilt over the tiles written since the last
 // build; ordered before the caller's screen on stream s.  False when it
 // cannot be allocated (the batch then runs the exact path).  Under stream
@@ -88,7 +88,14 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s)
     }
     if (cs != hipStreamCaptureStatusNone) {
         if (!c->d_shadow || c->sh_dirty_lo < c->sh_dirty_hi || !c->sh_ready) return false;
-        return hipEventSynchronize(c->sh_ready) == hipSuccess;
+        // (the host wait in relaxed mode: under a global- or thread-mode capture -- torch.cuda.graph's -- a
+        // synchronizing call from the capturing thread is refused and invalidates the capture; this one
+        // waits for work submitted before the capture and touches nothing the capture records)
+        hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+        if (hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) return false;
+        const bool ok = hipEventSynchronize(c->sh_ready) == hipSuccess;
+        (void)hipThreadExchangeStreamCaptureMode(&mode);
+        return ok;
     }
     const uint64_t tiles = tiles_of(c->capacity);
     if (!c->d_shadow) {
@@ -108,7 +115,9 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s)
         // scale S = the largest finite |x| / 127 of the rows written so far (one pass and
         // one host wait, at the shadow's first build); no rows / all zeros / an extreme
         // scale keep the bf16 shadow
-        bool i8 = c->ctx->opt.batch_screen == 2 && screen_i8_supported(c->dim) && c->high_water > 0;
+        // (an l2-squared corpus: always bf16, K3c-L2 is its one screen)
+        bool i8 = c->ctx->opt.batch_screen == 2 && c->metric != WVG_METRIC_L2 && screen_i8_supported(c->dim) &&
+                  c->high_water > 0;
         float sc[2] = {1.f, 1.f};
         if (i8) {
             uint32_t amax_bits = 0;
@@ -125,7 +134,7 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s)
             if (i8 && hipMemcpyAsync((uint32_t *)mx + 2, sc, 8, hipMemcpyHostToDevice, s) != hipSuccess) return fail();
             if (i8 && hipStreamSynchronize(s) != hipSuccess) return fail();  // (sc is on this stack)
         }
-        const uint32_t kbn = i8 ? c->dim / 64 : screen_kblocks(c->dim);
+        const uint32_t kbn = i8 ? c->dim / 64 : screen_kblocks(c->dim, c->metric == WVG_METRIC_L2);
         const size_t sbytes = (size_t)(tiles + 4) * kbn * 4 * 1024, nbytes = (size_t)(tiles + 4) * 64 * 4;
         if (hipMalloc(&sh, sbytes) != hipSuccess || hipMalloc(&nr, nbytes) != hipSuccess ||
             (i8 && hipMalloc(&er, nbytes) != hipSuccess) || hipMemsetAsync(sh, 0, sbytes, s) != hipSuccess ||
@@ -144,8 +153,9 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s)
         const hipError_t e =
             c->sh_i8 ? launch_shadow_build_i8((const float *)c->d_data, c->dim, c->sh_dirty_lo, c->sh_dirty_hi,
                                               c->d_shadow, c->d_norms, c->d_errs, c->d_nmax, s)
-                     : launch_shadow_build((const float *)c->d_data, c->dim, c->sh_dirty_lo, c->sh_dirty_hi,
-                                           c->d_shadow, c->d_norms, c->d_nmax, s);
+                     : launch_shadow_build((const float *)c->d_data, c->dim,
+                                           screen_kblocks(c->dim, c->metric == WVG_METRIC_L2), c->sh_dirty_lo,
+                                           c->sh_dirty_hi, c->d_shadow, c->d_norms, c->d_nmax, s);
         if (e != hipSuccess || hipEventRecord(c->sh_ready, s) != hipSuccess) return false;
         c->sh_dirty_lo = c->sh_dirty_hi = 0;
         return true;

@@ -158,7 +158,7 @@ struct ProfArm {
 // next screened search.  Callers hold the corpus lock exclusively.
 void shadow_mark(wvg_corpus *c, uint64_t t0, uint64_t t1);
 void shadow_free(wvg_corpus *c);
-// The bf16 shadow of an F32 dot / cosine corpus, ready for a screen on stream
+// The bf16 / int8 shadow of an F32 dot / cosine / l2-squared corpus, ready for a screen on stream
 // s (built or refreshed there, or waited for).  False: run the exact path.
 bool ensure_shadow(wvg_corpus *c, hipStream_t s);
 
@@ -168,7 +168,7 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s);
 // flagged-query list, the rescan's partial lists and the pilot's results.
 struct ScreenWs {
     size_t part = 0, cand = 0, keys = 0, gb = 0, qf = 0, k1 = 0, k2 = 0, em = 0, fl = 0, nf = 0, fbp = 0;
-    size_t pids = 0, pd = 0, pc = 0, kb = 0, css = 0, qinv = 0, total = 0;
+    size_t pids = 0, pd = 0, pc = 0, kb = 0, css = 0, qinv = 0, cq = 0, total = 0;
 };
 ScreenWs screen_ws(uint32_t nq, uint32_t k, uint32_t nrr, uint32_t kbn, uint32_t fb_groups);
 
@@ -176,8 +176,10 @@ struct SearchPlan {
     uint64_t tb = 0, te = 0;
     int groups = 1;      // scan: workgroups per query; gemm: row ranges (screen: K3c row ranges)
     bool gemm = false;   // K3 batched MFMA path
-    bool screen = false; // gemm via the K3c bf16 screen + exact rescore
-    int exact_groups = 1;   // screen: K3b's row ranges, if the shadow cannot be built
+    bool screen = false; // the bf16 / int8 screen + exact rescore (gemm: dot / cosine; !gemm: l2-squared, K3c-L2)
+    int exact_groups = 1;   // screen: the exact path's groups if the shadow cannot be built (K3b's row ranges;
+    bool exact_cosched = false;  // l2-squared has no K3b: the co-scheduled K1 / K1Q plan of the same batch)
+    int exact_mq = 0;
     uint32_t fb_groups = 0; // screen: K1 workgroups per flagged query's rescan
     uint32_t kbn = 0;       // screen: 32-element K blocks
     bool cosched = false; // PQ batch: co-scheduled K8e (ScanArgs::cosched)
@@ -195,7 +197,7 @@ struct SearchPlan {
     }
     size_t workspace_bytes(uint32_t nq, uint32_t k) const
     {
-        if (screen) return std::max(screen_ws(nq, k, (uint32_t)groups, kbn, fb_groups).total, gemm_bytes(nq, k, exact_groups, true));
+        if (screen) return std::max(screen_ws(nq, k, (uint32_t)groups, kbn, fb_groups).total, gemm_bytes(nq, k, exact_groups, gemm));
         return gemm_bytes(nq, k, groups, gemm);
     }
 };

@@ -110,7 +110,7 @@ struct wvg_corpus {
     float *d_centers = nullptr;    // [m][ks][ds]
     uint32_t pq_m = 0, pq_ks = 0, pq_ds = 0;
     bool pq_nan_free = false;      // the codebook has no NaN (launch_pq_encode)
-    // K3c's bf16 shadow of an F32 dot / cosine corpus (wvg_screen.hip), built on
+    // K3c's bf16 shadow of an F32 dot / cosine / l2-squared corpus (wvg_screen.hip), built on
     // the first batched search that uses it and kept in step with later writes
     void *d_shadow = nullptr;      // [tiles + 4][screen_kblocks][4][64] 16-B bf16 fragments
     float *d_norms = nullptr;      // [(tiles + 4) * 64] row-norm upper bounds
@@ -500,9 +500,12 @@ hipError_t launch_scan_f32_qlist(const ScanArgs &a, uint64_t *partials, int grou
 hipError_t launch_merge_lists_qlist(const uint64_t *partials, uint32_t nq, uint32_t nlists, uint32_t list_len,
                                     uint32_t k, uint64_t id_base, uint64_t *ids, float *dists, uint32_t *counts,
                                     const uint32_t *qlist, const uint32_t *nlist, hipStream_t s);
-// K3c bf16 MFMA screen + exact rescore (wvg_screen.hip).
+// K3c bf16 MFMA screen + exact rescore (wvg_screen.hip): dot / cosine, and
+// l2-squared (K3c-L2).
 constexpr int SCREEN_M = 16;  // lower bounds kept per (wave, query) and per (row range, query)
-inline uint32_t screen_kblocks(uint32_t dim) { return (dim + 63) / 64 * 2; }
+// 32-element K blocks of a bf16 shadow row: whole 64s for dot / cosine; an l2-squared corpus
+// (K3c-L2 only, which takes any count) has exactly dim / 32, so its shadow is 2 * dim + 4 bytes per row
+inline uint32_t screen_kblocks(uint32_t dim, bool l2 = false) { return l2 ? (dim + 31) / 32 : (dim + 63) / 64 * 2; }
 bool screen_supported(uint32_t dim, int metric, uint32_t k);
 uint32_t screen_row_ranges(uint32_t nq, uint64_t ntiles, int num_cus);
 #ifdef WVG_TOOLS
@@ -512,8 +515,8 @@ void coalesce_counters(uint64_t out[4], bool reset);
 void single_timing_read(uint64_t out[5], bool reset);
 void filtered_timing_read(uint64_t out[5], bool reset);
 #endif
-hipError_t launch_shadow_build(const float *tiled, uint32_t dim, uint64_t t0, uint64_t t1, void *shadow, float *norms,
-                               uint32_t *nmax, hipStream_t s);
+hipError_t launch_shadow_build(const float *tiled, uint32_t dim, uint32_t kbn, uint64_t t0, uint64_t t1, void *shadow,
+                               float *norms, uint32_t *nmax, hipStream_t s);
 // K3i (the int8 screen): dims it runs, the corpus scale's pass (largest finite
 // |x| of tiles [0, tiles) as float bits into *out) and the shadow build
 // (mx = {max norm, max error, S, 1 / S})
@@ -541,6 +544,9 @@ struct ScreenLaunch {
     bool i8 = false;
     const float *errs = nullptr;
     float *kb = nullptr, *css = nullptr, *qinv = nullptr;  // [nq_pad]
+    // K3c-L2 (an l2-squared corpus; bf16 shadow): per-query Cq [nq_pad]; cosine = 0
+    bool l2 = false;
+    float *cq = nullptr;
     uint32_t *gbound;      // [nq]
     uint64_t *partials;    // [nq][nrr][SCREEN_M]
     uint64_t *cand;        // [nq][nrr * SCREEN_M]
@@ -604,6 +610,7 @@ struct Tuning {
     int pq_encode_min3 = 1;  // PQ encode pair path: min3 argmin on NaN-free codebooks (1) or the
                              // reference's compare-and-select loop everywhere (0; A/B and parity)
     int screen_pilot = 16;   // K3c/K3d: tiles of the exact pilot scan that seeds the bound (0 = none; A/B)
+    int screen_pilot_l2 = 128;    // K3c-L2: tiles of its K1 pilot (l2-squared has no K3b pilot; 8k rows)
     int screen_pilot_gemm = 512;  // K3c/K3d: tiles of the K3b (exact fp32 MFMA) pilot, which replaces the K1
                                   // pilot (0 = the K1 pilot; A/B)
     int screen_round = 1;    // screen row ranges (tuning key 33): 1 = nrr * query blocks a multiple of the CUs

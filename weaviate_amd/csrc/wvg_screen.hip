@@ -9,6 +9,9 @@
 //   K3i  the int8 shadow at twice the MFMA rate ("The int8 screen"):
 //        screen_i8_kernel<KBN, 0>, 2 x 2 waves, d = 512 / 768 (the default
 //        there), and screen_ar_kernel<KBN, 0, true>, K3d's layout, d = 1024.
+//   K3c-L2  screen_l2_kernel: K3c's body with the l2-squared bound and
+//        threshold space (below, "K3c-L2"); the one screen of an l2-squared
+//        corpus, any d % 32 == 0, bit-identical to K1's l2_256 order.
 // A non-zero DIAG instantiates a timing / counting diagnostic of K3d or K3i
 // (tools build only).  Results are bit-identical to the exact path (K3b / K1,
 // the reference's AVX2-order dot_256):
@@ -137,11 +140,11 @@ __global__ __launch_bounds__(256) void shadow_norm_kernel(const float4 *__restri
     if ((threadIdx.x & 63) == 0) atomicMax(nmax, b);
 }
 
-hipError_t launch_shadow_build(const float *tiled, uint32_t dim, uint64_t t0, uint64_t t1, void *shadow, float *norms,
-                               uint32_t *nmax, hipStream_t s)
+hipError_t launch_shadow_build(const float *tiled, uint32_t dim, uint32_t kbn, uint64_t t0, uint64_t t1, void *shadow,
+                               float *norms, uint32_t *nmax, hipStream_t s)
 {
     if (t1 <= t0) return hipSuccess;
-    const uint32_t nch = f32_chunks(dim), kbn = screen_kblocks(dim);
+    const uint32_t nch = f32_chunks(dim);
     const uint64_t nfrag = (t1 - t0) * kbn * 4;
     hipLaunchKernelGGL(shadow_frag_kernel, dim3((unsigned)((nfrag * 64 + 255) / 256)), dim3(256), 0, s,
                        reinterpret_cast<const float4 *>(tiled), nch, kbn, t0, nfrag, reinterpret_cast<uint4 *>(shadow));
@@ -196,6 +199,48 @@ __global__ __launch_bounds__(256) void screen_qconst_kernel(const float *q, uint
     k1[qi] = K1;
     k2[qi] = K2;
     emax[qi] = __builtin_fmaf(__uint_as_float(*nmax), K1, K2);
+}
+
+// K3c-L2's per-query constants (below, "K3c-L2"): K1 / K2 as the dot's, Cq <=
+// |q|^2 - alpha Nq^2 - 2^-100 and Emax_q = E_tot at the corpus maximum norm,
+// from fp64 sums, rounded to the safe side.  A query whose norm bound is above
+// 2^56 or not finite: K1 = +inf, Cq = -inf (no fast rejection, every row a
+// candidate).
+__device__ __host__ inline double screen_l2_alpha(uint32_t dim) { return ((double)dim / 16.0 + 32.0) * 0x1p-24; }
+
+__global__ __launch_bounds__(256) void screen_qconst_l2_kernel(const float *q, uint32_t nq, uint32_t qpitch,
+                                                               uint32_t dim, uint32_t nq_pad, const uint32_t *nmax,
+                                                               float *k1, float *k2, float *emax, float *cq)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t qi = blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per query
+    if (qi >= nq_pad) return;
+    double ss = 0.0;
+    if (qi < nq)
+        for (uint32_t i = lane; i < dim; i += 64) {
+            const double x = q[(size_t)qi * qpitch + i];
+            ss += x * x;
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    if (lane) return;
+    const float nq_up = norm_upper(ss);
+    const float c = 0x1p-7f + 0x1p-15f + (float)dim * 0x1p-21f;
+    const double alpha = screen_l2_alpha(dim), beta = alpha + 0x1p-18;
+    const float nm = __uint_as_float(*nmax);
+    float K1 = c * nq_up + 0x1p-120f, K2 = 0x1p-120f * nq_up + 0x1p-110f;
+    float C = (float)(ss * (1.0 - 0x1p-19 - alpha) - 0x1p-100);
+    if (!(nq_up <= 0x1p56f)) {
+        K1 = __builtin_inff();
+        C = -__builtin_inff();
+    }
+    const double e1 = __builtin_fmaf(nm, K1, K2);
+    float E = (float)((2.0 * e1 + beta * ((double)nq_up * nq_up + (double)nm * nm) + 0x1p-99) * (1.0 + 0x1p-20));
+    if (qi >= nq) K1 = K2 = C = E = 0.f;
+    k1[qi] = K1;
+    k2[qi] = K2;
+    emax[qi] = E;
+    cq[qi] = C;
 }
 
 // ---------------------------------------------------------------------------
@@ -445,7 +490,7 @@ struct ScreenArgs {
     const uint64_t *allow;
     uint64_t allow_words, allow_t0;
     uint64_t tile_begin, tile_end;
-    uint32_t kbn;             // 32-element K blocks (even)
+    uint32_t kbn;             // 32-element K blocks (screen_kblocks)
     const uint4 *qfrag;       // [nq16][kbn][64]
     const float *k1, *k2, *emax;  // [nq_pad]
     const float *errs;        // K3i: [slots] row quantization-error norms (upper bounds)
@@ -508,6 +553,27 @@ __device__ __forceinline__ float sc_tau_k(float lower_k, float emax, int cosine)
     return t == t ? t : __builtin_inff();
 }
 
+// The l2-squared forms (K3c-L2, below).  u = (s - h) + E; the lower bound of
+// the distance is Cq - 2 u, clamped at 0 (the exact chain sums squares).  NaN
+// (a non-finite or huge row or query) -> -inf: always a candidate.
+__device__ __forceinline__ float sc_lower_l2(float u, float cq)
+{
+    const float l = cq - 2.0f * u;
+    if (l != l) return -__builtin_inff();
+    return __builtin_fmaxf(l, 0.0f);
+}
+
+// u-space threshold of a distance threshold tau: at or below the real
+// (Cq - tau) / 2, so u < sigma proves Cq - 2 u > tau (a superset test).
+__device__ __forceinline__ float sc_sigma_l2(float tau, float cq)
+{
+    if (!(tau < __builtin_inff())) return -__builtin_inff();
+    const float d = cq - tau;
+    const float s = __builtin_fmaf(-0x1p-22f, __builtin_fabsf(d), 0.5f * d) - 0x1p-120f;
+    return s == s ? s : -__builtin_inff();
+}
+// (sc_tau_k's dot form, cosine = 0, is the l2-squared one too: k-th lower + 2 Emax_q.)
+
 __device__ __forceinline__ float key_lower(uint64_t key) { return wvg_unord_f32((uint32_t)(key >> 32)); }
 
 // Exact insertion of one survivor (wave-uniform arguments) into a wave's list
@@ -522,11 +588,14 @@ __device__ __forceinline__ float key_lower(uint64_t key) { return wvg_unord_f32(
 // wait, which drains the stage prefetch once per exact-path row block.)
 typedef __attribute__((address_space(3))) uint64_t lds_u64;
 typedef __attribute__((address_space(3))) float lds_f32;
-__device__ __attribute__((noinline)) float sc_insert(lds_u64 *L, lds_f32 *WT, lds_f32 *WS, float emax, int K,
-                                                     int cosine, float u, uint32_t slot)
+// (one body: L2 = false is K3c's dot / cosine arithmetic, cq unused; L2 = true
+// the l2-squared form below, cosine unused)
+template <bool L2>
+__device__ __forceinline__ float sc_insert_body(lds_u64 *L, lds_f32 *WT, lds_f32 *WS, float emax, int K, int cosine,
+                                                float cq, float u, uint32_t slot)
 {
     const int lane = threadIdx.x & 63, M = SCREEN_M;
-    const float lower = sc_lower(u, cosine);
+    const float lower = L2 ? sc_lower_l2(u, cq) : sc_lower(u, cosine);
     if (!(lower <= *WT)) return *WS;
     const uint64_t key = ((uint64_t)wvg_ord_f32(lower) << 32) | slot;
     const uint64_t v = lane < M ? L[lane] : WVG_KEY_NONE;
@@ -539,9 +608,9 @@ __device__ __attribute__((noinline)) float sc_insert(lds_u64 *L, lds_f32 *WT, ld
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const uint64_t nk = L[K - 1], nm = L[M - 1];
     float t = *WT;
-    if (nk != WVG_KEY_NONE) t = fminf(t, sc_tau_k(key_lower(nk), emax, cosine));
+    if (nk != WVG_KEY_NONE) t = fminf(t, sc_tau_k(key_lower(nk), emax, L2 ? 0 : cosine));
     if (nm != WVG_KEY_NONE) t = fminf(t, key_lower(nm));
-    const float ws = sc_sigma(t, cosine);
+    const float ws = L2 ? sc_sigma_l2(t, cq) : sc_sigma(t, cosine);
     if (lane == 0) {
         *WT = t;
         *WS = ws;
@@ -549,6 +618,16 @@ __device__ __attribute__((noinline)) float sc_insert(lds_u64 *L, lds_f32 *WT, ld
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     return ws;
+}
+__device__ __attribute__((noinline)) float sc_insert(lds_u64 *L, lds_f32 *WT, lds_f32 *WS, float emax, int K,
+                                                     int cosine, float u, uint32_t slot)
+{
+    return sc_insert_body<false>(L, WT, WS, emax, K, cosine, 0.f, u, slot);
+}
+__device__ __attribute__((noinline)) float sc_insert_l2(lds_u64 *L, lds_f32 *WT, lds_f32 *WS, float emax, int K,
+                                                        float cq, float u, uint32_t slot)
+{
+    return sc_insert_body<true>(L, WT, WS, emax, K, 0, cq, u, slot);
 }
 
 // ---------------------------------------------------------------------------
@@ -639,7 +718,62 @@ __device__ __forceinline__ uint64_t sc_tile_mask(const ScreenArgs &a, uint64_t t
 __device__ unsigned long long g_screen_ctr[4];  // tools build: [0] row blocks, [1] slow-path entries, [2] insert calls
 #endif
 
-__global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
+// K3c-L2: K3c for l2-squared corpora -- the same workgroup, ring and MFMA
+// tile; the epilogue and the threshold space differ.
+//
+// The bound.  r = the exact fp32 chain of (q, x) in the AVX2 order (l2_256:
+// diff = fl(q - x), fma(diff, diff, acc) in 32 chains, the hadd tree); D =
+// |q - x|^2 = |q|^2 + |x|^2 - 2 q.x in real numbers; s = the bf16 MFMA dot;
+// Nq, Nx the norm upper bounds (sqrt of the fp64 square sum, (1 + 1e-6)).
+//   (a) every rounding of the chain is relative to a sum of non-negative
+//       terms, and a path through it has 2 (diff, squared) + d / 32 (a
+//       chain's fmas) + 6 (the accumulator adds and the hadd tree) of them:
+//       D (1 - c_a) - 2^-130 <= r <= D (1 + c_a) + 2^-130, c_a = (d / 32 + 12)
+//       2^-24 (denormal results: <= d 2^-149 in all); D <= 2 (Nq^2 + Nx^2).
+//   (b) |q.x - s| <= E1 = fma(Nx, K1q, K2q), K3c's constants (its c covers
+//       the bf16 operands and the MFMA's fp32 accumulation; the real dot has
+//       no AVX2-chain term, so the bound only gets looser).
+//   (c) the combine: h = fl(fl(Nx Nx) hg), w = fl(s - h), u = fl(w + E1),
+//       lower = fl(Cq - 2 u): three roundings relative to |s| + h and Nq^2 +
+//       2 |u|, in all <= 2^-21 (Nq^2 + Nx^2) -- relative to the operands, not
+//       to the (possibly tiny) result.
+// With alpha = 2 c_a + 2^-21 = (d / 16 + 32) 2^-24:
+//   2 h  <= |x|^2 - alpha Nx^2: hg = (1 - g) / 2 rounded down, g = alpha +
+//           2^-18 (|x|^2 >= Nx^2 (1 - 2.2e-6), two fp32 roundings of h);
+//   Cq   <= |q|^2 - alpha Nq^2 - 2^-100: the fp64 square sum times (1 - 2^-19
+//           - alpha) (its own error <= d 2^-53, the float cast 2^-24);
+// so lower <= D - 2 c_a (Nq^2 + Nx^2) - 2^-130 <= r.  The other side, with
+// beta = alpha + 2^-18:  r - lower <= 4 E1 + 2 beta (Nq^2 + Nx^2) + 2^-98 = 2
+// E_tot, E_tot = 2 E1 + beta (Nq^2 + Nx^2) + 2^-99, monotone in Nx: Emax_q =
+// E_tot at the corpus maximum norm (rounded up) bounds it for every row, and
+// tau = (k-th smallest lower) + 2 Emax_q holds as in K3c.  lower is clamped
+// at 0 (r >= 0: both sides keep holding).
+// Thresholds: u-space, per query: lower <= tau <=> u >= (Cq - tau) / 2;
+// sigma_q is that value rounded down (sc_sigma_l2), so the fast check stays
+// one compare per element and a superset test.
+// Non-finite and huge values: a row with Nx > 2^60 (inf: a NaN / inf row)
+// gets h = NaN, a query with Nq > 2^56 gets K1 = +inf and Cq = -inf; both
+// force the per-element path, where u is NaN or +inf and the lower bound
+// -inf: a candidate, rescored exactly, never a skip.  Inside the limits every
+// value above is finite (|s|, h, |u| < 2^122).
+struct ScreenL2Args {
+    ScreenArgs s;     // K3c's arguments (cosine = 0; k1 / k2 the dot's K1 / K2, emax the l2 Emax_q)
+    const float *cq;  // [nq_pad] Cq
+    float hg;         // (1 - g) / 2, rounded down
+};
+constexpr int SC_LDS_L2 = SC_LDS + SC_BQ * 4;  // + the workgroup's Cq
+
+// An element's u from its MFMA dot s, its error term e and (L2) its row's h
+template <bool L2>
+__device__ __forceinline__ float sc_u(float s, float e, float h)
+{
+    if constexpr (L2) return (s - h) + e;
+    else return s + e;
+}
+
+// The body of K3c (L2 = false: cqp / hg unused) and of K3c-L2.
+template <bool L2>
+__device__ __forceinline__ void screen_body(const ScreenArgs &a, const float *cqp, float hg)
 {
 #ifdef WVG_TOOLS
     uint32_t n_blk = 0, n_slow = 0, n_call = 0;
@@ -651,6 +785,7 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
     float *ck1 = sig + SC_WAVES * 32;                                      // [128]
     float *ck2 = ck1 + SC_BQ;
     float *cem = ck2 + SC_BQ;
+    float *ccq = cem + SC_BQ;                                              // [128] (L2 only)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -669,6 +804,14 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
     sc_copy_consts<false>(a, q0, SC_WAVES * 64, ck1, ck2, cem, nullptr, nullptr);
     sc_init_thresholds<32, 4, SC_WAVES>(a, q0, tid, cosine, tau, sig);  // 4 query quarters x 2 row halves
     for (int i = tid; i < SC_WAVES * 32 * M; i += SC_WAVES * 64) lists[i] = WVG_KEY_NONE;
+    if constexpr (L2) {
+        for (int i = tid; i < SC_BQ; i += SC_WAVES * 64) ccq[i] = cqp[q0 + (uint32_t)i];
+        __syncthreads();  // tau is in place: its u-space form with the query's Cq (slot (w, ql) = query 32 (w & 3) + ql)
+        for (int i = tid; i < SC_WAVES * 32; i += SC_WAVES * 64) {
+            const int qi = ((i >> 5) & 3) * 32 + (i & 31);
+            sig[i] = q0 + (uint32_t)qi >= a.nq ? __builtin_inff() : sc_sigma_l2(tau[i], ccq[qi]);
+        }
+    }
     __syncthreads();
     if (blk0 >= blk1) goto publish;
     {
@@ -856,6 +999,12 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
                 // (lane_force = +inf) or row forces the exact path below, which
                 // is the per-element test (NaN-safe) with the list insertions.
                 const bool all_valid = (vm[0] & vm[1]) == ~0ull;
+                // L2: the rows' h (a lower bound of |x|^2 / 2; NaN beyond the fast check's
+                // norm limit, so such a row's u is NaN: a candidate) and u = (s - h) + E
+                float hx[8];
+#pragma unroll
+                for (int nr = 0; nr < 8; nr++)
+                    hx[nr] = L2 ? (nrm[nr] <= 0x1p60f ? (nrm[nr] * nrm[nr]) * hg : __builtin_nanf("")) : 0.f;
                 float mx = -__builtin_inff(), mnr_a[8];
 #pragma unroll
                 for (int nr = 0; nr < 8; nr++) {
@@ -864,7 +1013,7 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
                     for (int mq = 0; mq < 2; mq++)
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
-                            const float u = acc[mq][nr][r] + __builtin_fmaf(nrm[nr], k1r[mq][r], k2r[mq][r]);
+                            const float u = sc_u<L2>(acc[mq][nr][r], __builtin_fmaf(nrm[nr], k1r[mq][r], k2r[mq][r]), hx[nr]);
                             mnr = __builtin_fmaxf(mnr, u - svr[mq][r]);
                         }
                     mnr = nrm[nr] <= 0x1p60f ? mnr : __builtin_inff();
@@ -892,7 +1041,7 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
                         const uint64_t m64 = m16 * 0x0001000100010001ull;
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
-                            const float u = acc[mq][nr][r] + __builtin_fmaf(nrm[nr], k1r[mq][r], k2r[mq][r]);
+                            const float u = sc_u<L2>(acc[mq][nr][r], __builtin_fmaf(nrm[nr], k1r[mq][r], k2r[mq][r]), hx[nr]);
                             uint64_t pass = __ballot(!(u < svr[mq][r])) & m64 & qlive[mq][r];
                             while (pass) {  // rare after the first row blocks of a range
                                 const int src = __builtin_ctzll(pass);
@@ -904,7 +1053,11 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a)
 #ifdef WVG_TOOLS
                                 n_call++;
 #endif
-                                const float ws_now =
+                                float ws_now;
+                                if constexpr (L2)
+                                    ws_now = sc_insert_l2((lds_u64 *)(WL + ql * M), (lds_f32 *)(WT + ql), (lds_f32 *)(WS + ql), cem[32 * wq + ql], K, ccq[32 * wq + ql], us, slot);
+                                else
+                                    ws_now =
                                     sc_insert((lds_u64 *)(WL + ql * M), (lds_f32 *)(WT + ql), (lds_f32 *)(WS + ql), cem[32 * wq + ql], K, cosine, us, slot);
                                 // the other lanes of this 16-lane group hold the same query
                                 const uint64_t grp = 0xFFFFull << (16 * (src >> 4));
@@ -959,6 +1112,13 @@ publish:
             atomicMin(a.gbound + q, wvg_ord_f32(t));
         }
     }
+}
+
+__global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a) { screen_body<false>(a, nullptr, 0.f); }
+
+__global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_l2_kernel(ScreenL2Args a)
+{
+    screen_body<true>(a.s, a.cq, a.hg);
 }
 
 // ---------------------------------------------------------------------------
@@ -2193,6 +2353,12 @@ __global__ __launch_bounds__(256) void screen_collect_kernel(const uint64_t *par
 }
 
 
+__global__ __launch_bounds__(256) void screen_fill_kernel(uint32_t *p, uint32_t n, uint32_t v)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
 __global__ __launch_bounds__(256) void screen_pilot_list_kernel(uint32_t *flist, uint32_t nq, uint32_t *nflag)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -2210,12 +2376,12 @@ __global__ __launch_bounds__(256) void screen_pilot_seed_kernel(const float *dis
     if (t < __builtin_inff()) atomicMin(gbound + q, wvg_ord_f32(t));
 }
 
-// Whether K3c applies (the bound needs dim % 32 == 0 only for the fragment
+// Whether K3c (dot / cosine) or K3c-L2 (l2-squared) applies (the bound needs dim % 32 == 0 only for the fragment
 // layout; k <= SCREEN_M for the list to hold the k-th key).
 bool screen_supported(uint32_t dim, int metric, uint32_t k)
 {
     return dim % 32 == 0 && dim > 0 && k > 0 && k <= (uint32_t)SCREEN_M &&
-           (metric == WVG_M_DOT || metric == WVG_M_COSINE);
+           (metric == WVG_M_DOT || metric == WVG_M_COSINE || metric == WVG_M_L2);
 }
 
 #ifdef WVG_TOOLS
@@ -2321,16 +2487,45 @@ static const ScreenKernel *pick_screen_kernel(bool i8, uint32_t kbn, int variant
 
 hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
 {
-    const bool i8 = L.i8 && screen_i8_supported(L.dim);
-    const uint32_t kbn = i8 ? L.dim / 64 : screen_kblocks(L.dim);  // (K3i: 64-deep int8 K blocks)
+    const bool i8 = !L.l2 && L.i8 && screen_i8_supported(L.dim);  // (an l2-squared corpus has the bf16 shadow)
+    const uint32_t kbn = i8 ? L.dim / 64 : screen_kblocks(L.dim, L.l2);  // (K3i: 64-deep int8 K blocks)
     const uint32_t nq_pad = (L.nq + SC_BQ - 1) / SC_BQ * SC_BQ, nqb = nq_pad / SC_BQ;
     hipError_t e;
     // the kernel first: an unsupported (variant, diag) starts nothing
-    const ScreenKernel *sk = pick_screen_kernel(i8, kbn, tuning().screen_variant, tuning().screen_diag);
-    if (!sk) return hipErrorInvalidValue;
+    // (l2-squared: K3c-L2 whatever the variant; a diagnostic has no L2 form)
+    const ScreenKernel *sk = L.l2 ? pick_screen_kernel(false, kbn, 1, 0)
+                                  : pick_screen_kernel(i8, kbn, tuning().screen_variant, tuning().screen_diag);
+    if (!sk || (L.l2 && (tuning().screen_diag != 0 || !L.cq))) return hipErrorInvalidValue;
     void (*const kern)(ScreenArgs) = sk->fn;
-    const uint32_t lds = sk->lds, threads = sk->threads;
-    if (i8) {
+    const uint32_t lds = L.l2 ? (uint32_t)SC_LDS_L2 : sk->lds, threads = sk->threads;
+    if (L.l2) {
+        static const bool attr_l2 =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_l2_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_L2) == hipSuccess;
+        (void)attr_l2;
+    }
+    // one launch of the chosen kernel over the ranges in x (K3c-L2 wraps x with Cq and hg)
+    const float hg = L.l2 ? (float)((1.0 - (screen_l2_alpha(L.dim) + 0x1p-18)) * 0.5 * (1.0 - 0x1p-23)) : 0.f;
+    auto launch = [&](const ScreenArgs &x, uint32_t blocks, hipEvent_t e0, hipEvent_t e1) {
+        if (L.l2) {
+            const ScreenL2Args xl{x, L.cq, hg};
+            if (e0 || e1)
+                hipExtLaunchKernelGGL(screen_l2_kernel, dim3(blocks), dim3(threads), lds, s, e0, e1, 0u, xl);
+            else
+                hipLaunchKernelGGL(screen_l2_kernel, dim3(blocks), dim3(threads), lds, s, xl);
+        } else if (e0 || e1) {
+            hipExtLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, s, e0, e1, 0u, x);
+        } else {
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, s, x);
+        }
+    };
+    if (L.l2) {
+        hipLaunchKernelGGL(screen_qfrag_kernel, dim3((unsigned)(((uint64_t)nq_pad / 16 * kbn * 64 + 255) / 256)),
+                           dim3(256), 0, s, L.queries, L.nq, L.qpitch, L.dim, kbn, nq_pad / 16,
+                           reinterpret_cast<uint4 *>(L.qfrag));
+        hipLaunchKernelGGL(screen_qconst_l2_kernel, dim3(nq_pad / 4), dim3(256), 0, s, L.queries, L.nq, L.qpitch, L.dim,
+                           nq_pad, L.nmax, L.k1, L.k2, L.emax, L.cq);
+    } else if (i8) {
         // K3i: per-query scale and bound constants first, then the int8 fragments at that scale
         hipLaunchKernelGGL(screen_qconst_i8_kernel, dim3(nq_pad / 4), dim3(256), 0, s, L.queries, L.nq, L.qpitch,
                            L.dim, nq_pad, L.cosine, L.nmax, reinterpret_cast<const float *>(L.nmax + 2), L.k1, L.k2,
@@ -2346,13 +2541,18 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
         hipLaunchKernelGGL(screen_qconst_kernel, dim3(nq_pad / 4), dim3(256), 0, s, L.queries, L.nq, L.qpitch, L.dim,
                            nq_pad, L.cosine, L.nmax, L.k1, L.k2, L.emax);
     }
-    if ((e = hipMemsetAsync(L.gbound, 0xFF, (size_t)L.nq * 4, s)) != hipSuccess) return e;
+    // (kernels, not memsets, reset the bounds and the flag count: a captured device search replays
+    // them in order with the launches around them)
+    hipLaunchKernelGGL(screen_fill_kernel, dim3((L.nq + 255) / 256), dim3(256), 0, s, L.gbound, L.nq, 0xFFFFFFFFu);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     // profiling: one event pair spans every phase and the seeds between them (taken
     // before the pilot, whose K3b launch would otherwise bind them)
     const LaunchEvents ev = armed_events();
     armed_events() = LaunchEvents{};
-    const uint64_t pilot_tiles = (uint64_t)std::max(tuning().screen_pilot, 0);
-    const uint64_t pilot_gemm_tiles = (uint64_t)std::max(L.i8 ? tuning().screen_pilot_gemm_i8 : tuning().screen_pilot_gemm, 0);
+    const uint64_t pilot_tiles = (uint64_t)std::max(L.l2 ? tuning().screen_pilot_l2 : tuning().screen_pilot, 0);
+    // (no K3b for l2-squared: its pilot is the K1 one)
+    const uint64_t pilot_gemm_tiles =
+        L.l2 ? 0 : (uint64_t)std::max(L.i8 ? tuning().screen_pilot_gemm_i8 : tuning().screen_pilot_gemm, 0);
     // Screen pilot: short ranges of the screen itself over the first sp_tiles tiles
     // (one workgroup per CU), lists into the pilot scratch ([nq][sp_rr][SCREEN_M]),
     // then one exact seed from them (below, once the kernel is chosen)
@@ -2412,7 +2612,8 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
                            L.pilot_counts, L.nq, L.k, L.gbound);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if ((e = hipMemsetAsync(L.nflag, 0, 4, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(screen_fill_kernel, dim3(1), dim3(256), 0, s, L.nflag, 1u, 0u);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     ScreenArgs a{};
     a.shadow = reinterpret_cast<const uint4 *>(L.shadow);
     a.norms = L.norms;
@@ -2458,7 +2659,7 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
         f.rr0 = 0;
         f.nrr_l = sp_rr;
         f.partials = L.pilot_part;
-        hipLaunchKernelGGL(kern, dim3(nqb * sp_rr), dim3(threads), lds, s, f);
+        launch(f, nqb * sp_rr, nullptr, nullptr);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if ((e = launch_seed_exact(L.metric, L.queries, L.qpitch, L.data, L.dim, L.nchunks, L.pilot_part,
                                    sp_rr * SCREEN_M, SCREEN_M, sp_rr, L.nq, L.k, L.gbound, s)) != hipSuccess)
@@ -2509,10 +2710,7 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
         a.rr0 = bounds[ph];
         a.nrr_l = bounds[ph + 1] - bounds[ph];
         const hipEvent_t e0 = ph == 0 ? ev.start : nullptr, e1 = ph + 1 == nph ? ev.stop : nullptr;
-        if (e0 || e1)
-            hipExtLaunchKernelGGL(kern, dim3(nqb * a.nrr_l), dim3(threads), lds, s, e0, e1, 0u, a);
-        else
-            hipLaunchKernelGGL(kern, dim3(nqb * a.nrr_l), dim3(threads), lds, s, a);
+        launch(a, nqb * a.nrr_l, e0, e1);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (ph + 1 < nph) {
             if (seed_exact) {

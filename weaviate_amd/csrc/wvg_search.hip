@@ -207,6 +207,7 @@ ScreenWs screen_ws(uint32_t nq, uint32_t k, uint32_t nrr, uint32_t kbn, uint32_t
     w.kb = cv.take(nq_pad * 4);  // K3i's per-query constants
     w.css = cv.take(nq_pad * 4);
     w.qinv = cv.take(nq_pad * 4);
+    w.cq = cv.take(nq_pad * 4);  // K3c-L2's
     w.total = cv.off;
     return w;
 }
@@ -268,6 +269,24 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
         p.groups = pq_cosched_groups(p.mq ? (nq + p.mq - 1) / p.mq : nq,
                                      std::max(scan_groups_for(a1, c->ctx->num_cus), 8));
     }
+    // K3c-L2: an l2-squared batch takes the bf16 screen + exact rescore exactly when a dot batch of
+    // the same shape would take K3c (a batch: nq >= 2).  There is no K3b for l2-squared, so the plan
+    // above -- the co-scheduled K1 / K1Q -- stays as the path of a shadow that cannot be used.
+    if (gemm_ok && c->kind == WVG_KIND_F32 && c->metric == WVG_METRIC_L2 && mn > 0 && nq >= mn && nq >= 2 &&
+        !c->ctx->order512 && c->ctx->opt.batch_screen && screen_supported(c->dim, c->metric, k) && c->dim % 4 == 0 &&
+        !c->sh_failed) {
+        p.screen = true;
+        p.exact_groups = p.groups;
+        p.exact_cosched = p.cosched;
+        p.exact_mq = p.mq;
+        p.cosched = false;
+        p.mq = 0;
+        p.groups = (int)screen_row_ranges(nq, std::max<uint64_t>(1, p.te - p.tb), c->ctx->num_cus);
+        ScanArgs a1 = a;
+        a1.nq = 1;
+        p.fb_groups = (uint32_t)std::min(scan_groups_for(a1, c->ctx->num_cus), c->ctx->num_cus);
+        p.kbn = screen_kblocks(c->dim, true);
+    }
     return p;
 }
 
@@ -317,6 +336,8 @@ static int run_screen(wvg_corpus *c, const ScanArgs &a, const SearchPlan &p, cha
     L.kb = (float *)(ws + w.kb);
     L.css = (float *)(ws + w.css);
     L.qinv = (float *)(ws + w.qinv);
+    L.l2 = c->metric == WVG_METRIC_L2;
+    L.cq = (float *)(ws + w.cq);
     uint64_t *keys = (uint64_t *)(ws + w.keys);
     L.metric = c->metric;
     L.data = (const float *)c->d_data;
@@ -341,7 +362,7 @@ static int run_screen(wvg_corpus *c, const ScanArgs &a, const SearchPlan &p, cha
 // (a filtered query too: its allow window is copied with the call, the scan masks tiles with it)
 static bool inlaunch_single(const wvg_corpus *c, uint32_t nq, const SearchPlan &p)
 {
-    return nq == 1 && !p.gemm && !p.cosched && c->kind == WVG_KIND_F32 && tuning().pipeline_mode == 1;
+    return nq == 1 && !p.gemm && !p.screen && !p.cosched && c->kind == WVG_KIND_F32 && tuning().pipeline_mode == 1;
 }
 
 int run_search(wvg_corpus *c, const void *d_q, uint32_t qpitch, uint32_t nq, uint32_t k, const uint64_t *d_allow,
@@ -372,7 +393,7 @@ int run_search(wvg_corpus *c, const void *d_q, uint32_t qpitch, uint32_t nq, uin
     a.order512 = c->ctx->order512;
     a.plain = plain_loads(c, p.tb, p.te);
     a.cache_tail256 = k1_cache_tail(c, p.tb, p.te);
-    if (!p.gemm) a.reverse = next_direction(c, 1);
+    if (!p.gemm && !p.screen) a.reverse = next_direction(c, 1);
     if (p.cosched && c->kind == WVG_KIND_F32) {  // K1 COS: partners read the rows from L2
         a.plain = 1;
         a.cache_tail256 = 0;
@@ -383,9 +404,11 @@ int run_search(wvg_corpus *c, const void *d_q, uint32_t qpitch, uint32_t nq, uin
             if (arm.rc) return arm.rc;
             return run_screen(c, a, p, reinterpret_cast<char *>(partials), ids, dists, counts, s);
         }
-        SearchPlan pe = p;  // no shadow: the exact MFMA path over the same workspace
+        SearchPlan pe = p;  // no shadow: the exact path (K3b; l2-squared: K1 / K1Q) over the same workspace
         pe.screen = false;
         pe.groups = p.exact_groups;
+        pe.cosched = p.exact_cosched;
+        pe.mq = p.exact_mq;
         return run_search(c, d_q, qpitch, nq, k, d_allow, pe, partials, ids, dists, counts, s, sl, nullptr, so);
     }
     if (sl && inlaunch_single(c, nq, p)) {
@@ -1358,6 +1381,28 @@ int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg
     std::shared_lock<std::shared_mutex> lk(c->rw);
     uint32_t seed_tiles;
     *out = stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k, &seed_tiles);
+    return WVG_OK;
+}
+
+int wvg_search_batch_plan(wvg_corpus *c, uint32_t nq, uint32_t k, int shared_allow_list, wvg_batch_plan *out)
+{
+    if (!c || !out) return fail(WVG_ERR_INVALID, "null corpus / plan");
+    *out = wvg_batch_plan{0u, 0u, 0u, 0u};
+    if (nq == 0 || k == 0 || k > MAX_K) return WVG_OK;  // (k > 256: select + sort in HBM, no matrix path)
+    std::shared_lock<std::shared_mutex> lk(c->rw);
+    // one allow list shared by the batch masks tiles inside the same kernels: the route does not depend on it
+    (void)shared_allow_list;
+    const SearchPlan p = plan_search(c, nq, k, nullptr, 0);
+    if (p.empty) return WVG_OK;
+    out->matrix = p.gemm || p.screen;
+    if (p.screen) {
+        // the shadow a first screened search would build (ensure_shadow), or the one that exists
+        const bool i8 = c->d_shadow ? c->sh_i8
+                                    : c->ctx->opt.batch_screen == 2 && c->metric != WVG_METRIC_L2 &&
+                                          screen_i8_supported(c->dim);
+        out->screen = i8 ? 2u : 1u;
+        out->shadow_bytes_per_row = i8 ? c->dim + 8 : 64 * screen_kblocks(c->dim, c->metric == WVG_METRIC_L2) + 4;
+    }
     return WVG_OK;
 }
 

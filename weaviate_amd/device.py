@@ -13,7 +13,7 @@ from ctypes import byref, c_int, c_uint64, c_void_p
 import numpy as np
 
 from . import _lib
-from ._lib import StreamPlan, check, fptr, u32ptr, u64ptr
+from ._lib import BatchPlan, StreamPlan, check, fptr, u32ptr, u64ptr
 
 
 def device_count() -> int:
@@ -255,6 +255,13 @@ class Corpus:
         sp = StreamPlan()
         check(self.lib.wvg_search_device_pipelined_plan(self.handle, nq, k, byref(sp)))
         return {name: int(getattr(sp, name)) for name, _ in StreamPlan._fields_}
+
+    def batch_plan(self, nq: int, k: int, allow: bool = False) -> dict:
+        """wvg_search_batch_plan: the route a batch of nq queries takes on this corpus -- {matrix, screen,
+        shadow_bytes_per_row} (struct wvg_batch_plan; allow: the batch shares one allow list).  Host only."""
+        bp = BatchPlan()
+        check(self.lib.wvg_search_batch_plan(self.handle, nq, k, 1 if allow else 0, byref(bp)))
+        return {name: int(getattr(bp, name)) for name, _ in BatchPlan._fields_ if name != "reserved"}
 
     def search_by_distance(self, query, target: float, max_limit: int = -1, allow=None, capacity: int | None = None):
         """wvg_search_by_distance: (ids, dists) of every row within `target`

@@ -956,6 +956,8 @@ func (x *Corpus) SearchDevice(b DeviceBuffers, nq, k int) error {
 }
 
 // SearchDevicePipelined: nq single-query scans in one query-stream launch.
+// F32 and BQ corpora (BQ: b.Queries are the raw float rows; per query the Hamming
+// top-k, (distance, docID)-ordered, the queries sharing each read of the codes).
 func (x *Corpus) SearchDevicePipelined(b DeviceBuffers, nq, k int) error {
 	defer pin(x)()
 	return err(C.wvg_search_device_pipelined(x.h, (*C.float)(b.Queries), C.uint32_t(nq), C.uint32_t(k),
@@ -974,7 +976,8 @@ type StreamPlan struct {
 }
 
 // DevicePipelinedPlan: the StreamPlan of a call with nq queries and k results
-// each.  Host only: nothing is launched.
+// each.  Host only: nothing is launched.  F32 and BQ corpora (BQ: 8 queries per
+// pass for nq >= 2 with cache_reuse on, never seeded or screened).
 func (x *Corpus) DevicePipelinedPlan(nq, k int) (StreamPlan, error) {
 	defer pin(x)()
 	if nq < 0 || k < 0 {
@@ -1063,7 +1066,7 @@ func (c *Ctx) CopyWordsToDevice(dst unsafe.Pointer, src []uint64, s unsafe.Point
 
 // SearchDevicePipelinedFiltered: SearchDevicePipelined with one allow list per
 // query (a `where` filter's AllowList, V/flat/index.go:423-449), read on the
-// device: per query the results of Search with that list.
+// device: per query the results of Search with that list.  F32 and BQ corpora.
 func (x *Corpus) SearchDevicePipelinedFiltered(b DeviceBuffers, nq, k int, allow DeviceAllow) error {
 	defer pin(x)()
 	if nq < 0 || k < 0 {

@@ -335,7 +335,10 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * UINT64_MAX, dists +inf, counts 0 (as wvg_search).  wvg_search_device
  * takes F32, BQ and PQ corpora (d_queries: float [nq][dim]; BQ codes and PQ
  * LUTs are built on the device -- size the workspace after the PQ codebook
- * is set); wvg_search_device_pipelined takes F32 corpora.                  */
+ * is set); wvg_search_device_pipelined takes F32 and BQ corpora.  For a BQ
+ * corpus the size is the largest of wvg_search_device's layout and the
+ * pipelined ones (status block, partial lists [nq][row ranges][k], the
+ * queries' codes); it never got smaller than it was.                       */
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k);
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                       uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
@@ -358,9 +361,21 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
  * combines them; no workgroup waits for another.  Everywhere else (one query, other metrics, d = 4, the
  * AVX-512 order, cache_reuse = 0) every query is one full scan of the corpus:
  * the scan workgroups walk the queries back to back and one extra workgroup
- * merges each query's lists while the scan moves on.  F32 corpora; same
- * workspace size rule; outputs as wvg_search_device.
- * wvg_search_device_pipelined_plan tells which of the two a call takes.    */
+ * merges each query's lists while the scan moves on.  Same workspace size
+ * rule; outputs as wvg_search_device.
+ * BQ corpora (d_queries: float [nq][dim] of any dim, as wvg_search_device
+ * takes them -- normalized by the caller for cosine; the sign codes are made
+ * on the device): with nq >= 2 and cache_reuse on, two launches on `stream`,
+ * a scan whose waves load every 64-row tile of codes once per pass of 8
+ * queries and score it against each of them (XOR + popcount, the query words
+ * wave-uniform), then the merge of the partial lists; no workgroup waits for
+ * another and the status block is not touched.  One query, or cache_reuse =
+ * 0, is wvg_search_device's route for that nq.  Per query the result is
+ * wvg_search_device's for that query alone: the (Hamming distance, docID)-
+ * lexicographic top-k, ascending.  The order the reference's heap keeps
+ * inside ties is what wvg_search_bq_candidates returns, and that needs the
+ * host; the rescore of the candidates stays with wvg_rescore or the caller.
+ * wvg_search_device_pipelined_plan tells which route a call takes.          */
 int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                                 uint64_t *d_ids, float *d_dists, uint32_t *d_counts,
                                 void *d_workspace, size_t workspace_bytes, void *stream);
@@ -385,10 +400,13 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
  * a query scores only the rows its list allows, and a 64-row tile that no
  * query of the pass allows is skipped before it is read.  Everywhere else
  * (one query, other metrics, d = 4, cache_reuse = 0) every query is one scan
- * with its own window, followed by a merge launch for nq >= 2.  Otherwise as
- * wvg_search_device_pipelined: F32 corpora, asynchronous on `stream`, no
- * allocation, no host synchronization, capturable; the same workspace rule
- * (wvg_search_workspace_size is unchanged).                                 */
+ * with its own window, followed by a merge launch for nq >= 2.  BQ corpora:
+ * the shared-row BQ scan masks each query's rows with its own words and does
+ * not load a tile no query of the pass allows; with one query or cache_reuse
+ * = 0, one Hamming scan launch per query, each with its window, and one
+ * merge.  Otherwise as wvg_search_device_pipelined: F32 and BQ corpora,
+ * asynchronous on `stream`, no allocation, no host synchronization,
+ * capturable; the same workspace rule.                                      */
 int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                                          const uint64_t *d_allow, uint64_t allow_stride,
                                          uint64_t allow_first_id, uint64_t *d_ids, float *d_dists,
@@ -398,8 +416,10 @@ int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, 
  * that sizes its batches to fill whole passes.  Host only: no device call,
  * nothing launched; computed by the functions the search itself routes with.
  * With an allow list the same call shares rows under the same conditions.
- * nq == 0, k == 0 or an empty corpus: passes = 0.  Errors as the search's
- * (k > 256, a corpus that is not F32, dim % 4 != 0).                        */
+ * nq == 0, k == 0 or an empty corpus: passes = 0.  A BQ corpus: {1, Q,
+ * ceil(nq / Q), 0, 0} with the scan's Q (8) for nq >= 2 and cache_reuse on,
+ * {0, 1, nq, 0, 0} otherwise.  Errors as the search's (k > 256, a PQ corpus,
+ * an F32 corpus with dim % 4 != 0).                                         */
 typedef struct wvg_stream_plan {
     uint32_t shared_rows;      /* 1: the shared-row kernel; 0: one scan per query */
     uint32_t queries_per_pass; /* queries that share one read of the rows (1 if !shared_rows) */

@@ -468,6 +468,29 @@ hipError_t launch_scan_bq(const ScanArgs &a, uint64_t *partials, int groups, hip
 constexpr int BQ_SCAN_WAVES = 4;
 constexpr size_t BQ_EMIT_LDS_MAX = 128u << 10;
 hipError_t launch_scan_bq_emit(const ScanArgs &a, uint64_t *partials, int groups, bool lds, hipStream_t s);
+// Shared-row query stream of a BQ corpus (scan_bq_qshare_kernel, wvg_bq_qshare.hip): one launch of
+// (groups, passes) 4-wave workgroups; pass p scores queries [p Q, min(nq, (p + 1) Q)), Q =
+// bq_qshare_queries_per_pass(), against every tile of its range, each tile loaded once, in direction
+// (reverse + p) & 1, and leaves one k-list per (query, range) in partials [nq][groups][k].  The caller
+// merges them (launch_merge_lists) by stream order.  allow: null, or per-query allow words with
+// QShareFilt's meaning (query q's word of tile t is allow[q * allow_stride + (t - allow_t0)] if
+// t - allow_t0 < allow_stride, unsigned, and 0 otherwise); a tile no query of the pass has a live
+// allowed row in is not loaded.
+struct BQShareArgs {
+    const void *data;          // tiled codes
+    const uint64_t *valid;     // one word per tile
+    const uint64_t *queries;   // [nq][qpitch] code words, qpitch = 2 * nchunks (padding zero)
+    uint64_t *partials;
+    const uint64_t *allow;
+    uint64_t allow_stride, allow_t0;
+    uint64_t tile_begin, tile_end;
+    uint32_t nchunks, qpitch, nq, k;
+    uint32_t reverse;          // direction of pass 0
+    uint32_t plain;            // code loads with the default cache policy instead of non-temporal
+};
+uint32_t bq_qshare_queries_per_pass(uint32_t nchunks, uint32_t k);
+uint32_t bq_qshare_groups(uint64_t ntiles, int num_cus);
+hipError_t launch_scan_bq_qshare(const BQShareArgs &a, uint32_t groups, hipStream_t s);
 // Heap replay (wvg_replay.hip).  prefix: per query, thr[q][g] = the k-th smallest
 // distance of ranges 0..g-1's lists (partials [nq][groups][k], ascending; +inf
 // while fewer than k rows precede range g).  filter: each wave's emitted keys

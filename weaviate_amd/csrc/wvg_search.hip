@@ -1370,15 +1370,74 @@ static wvg_stream_plan stream_plan(const wvg_corpus *c, const SearchPlan &p1, ui
     return sp;
 }
 
+// ---- BQ corpora in the pipelined search ----------------------------------------------------------
+// Two or more queries in a context with cache_reuse on take the shared-row BQ scan
+// (scan_bq_qshare_kernel, wvg_bq_qshare.hip) and the list merge, two launches on the caller's
+// stream.  One query, or cache_reuse = 0 ("one full scan per query", as for F32), is
+// wvg_search_device's route for that nq; with allow lists one K5 launch per query, each with
+// its own window, then one merge.  Results are the (Hamming distance, docID)-lexicographic
+// top-k on every route.
+static bool bq_stream_route(const wvg_corpus *c, uint32_t nq)
+{
+    if (tuning().qshare < 0) return false;
+    return nq >= 2 && c->kind == WVG_KIND_BQ && c->ctx->opt.cache_reuse;
+}
+
+static wvg_stream_plan bq_stream_plan(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k)
+{
+    wvg_stream_plan sp{0u, 1u, p1.empty ? 0u : nq, 0u, 0u};
+    if (p1.empty || !bq_stream_route(c, nq)) return sp;
+    sp.shared_rows = 1;
+    sp.queries_per_pass = bq_qshare_queries_per_pass(c->nchunks, k);
+    sp.passes = (nq + sp.queries_per_pass - 1) / sp.queries_per_pass;
+    return sp;
+}
+
+// Lists per query of a pipelined BQ call over the tiles of p1: the shared-row scan's row ranges, or
+// the single-query K5 grid of the per-query launches.
+static uint32_t bq_stream_groups(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq)
+{
+    return bq_stream_route(c, nq) ? bq_qshare_groups(p1.te - p1.tb, c->ctx->num_cus) : (uint32_t)p1.groups;
+}
+
+// Workspace of a pipelined BQ call (after the status block): partial lists [nq][groups][k], the
+// queries' codes at the scan's pitch, the encoder's dense output.
+struct BqStreamLayout {
+    size_t partials = 0, qcodes = 0, codes = 0, total = 0;
+};
+static BqStreamLayout bq_stream_layout(const wvg_corpus *c, uint32_t nq, uint32_t k, uint32_t groups)
+{
+    BqStreamLayout l;
+    l.partials = WS_STATUS_BYTES;
+    l.qcodes = l.partials + align_up((size_t)nq * groups * k * 8, 256);
+    l.codes = l.qcodes + align_up((size_t)nq * bq_chunks(c->dim) * 16, 256);
+    l.total = l.codes + align_up((size_t)nq * bq_words(c->dim) * 8, 256);
+    return l;
+}
+
+// Shared-row code loads: the default cache policy while the scanned codes are within a few times
+// the Infinity Cache, so that the next pass (it walks the other way) finds part of them there;
+// non-temporal beyond.  The threshold is K1's (plain_loads), not measured for codes.
+static int bq_stream_plain(const wvg_corpus *c, uint64_t tb, uint64_t te)
+{
+    if (tuning().k1_loads) return plain_loads(c, tb, te);
+    return (te - tb) * (uint64_t)c->nchunks * 1024ull <= (800ull << 20);
+}
+
 int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg_stream_plan *out)
 {
     if (!c || !out) return fail(WVG_ERR_INVALID, "null corpus / plan");
     if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "k above 256 is not supported by the fused top-k");
-    if (c->kind != WVG_KIND_F32) return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32 corpora");
-    if (c->dim % 4 != 0) return fail(WVG_ERR_UNSUPPORTED, "device search needs dim % 4 == 0");
+    if (c->kind != WVG_KIND_F32 && c->kind != WVG_KIND_BQ)
+        return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32 and BQ corpora");
+    if (c->kind == WVG_KIND_F32 && c->dim % 4 != 0) return fail(WVG_ERR_UNSUPPORTED, "device search needs dim % 4 == 0");
     *out = wvg_stream_plan{0u, 1u, 0u, 0u, 0u};
     if (nq == 0 || k == 0) return WVG_OK;
     std::shared_lock<std::shared_mutex> lk(c->rw);
+    if (c->kind == WVG_KIND_BQ) {
+        *out = bq_stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k);
+        return WVG_OK;
+    }
     uint32_t seed_tiles;
     *out = stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k, &seed_tiles);
     return WVG_OK;
@@ -1412,6 +1471,12 @@ size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
     const uint32_t kk = std::max<uint32_t>(k, 1);
     SearchPlan p = plan_search(c, nq, k, nullptr, 0);
     const size_t dev = WS_STATUS_BYTES + align_up(p.workspace_bytes(nq, kk), 256) + device_query_bytes(c, nq);
+    if (c->kind == WVG_KIND_BQ) {  // pipelined: the shared-row layout, or the per-query launches' (it only grows)
+        const SearchPlan pb = plan_search(c, 1, k, nullptr, 0);
+        const size_t shared = bq_stream_layout(c, nq, kk, bq_qshare_groups(pb.te - pb.tb, c->ctx->num_cus)).total;
+        const size_t single = bq_stream_layout(c, nq, kk, (uint32_t)pb.groups).total;
+        return std::max({dev, shared, single});
+    }
     if (c->kind != WVG_KIND_F32) return dev;  // no pipelined mode
     SearchPlan p1 = plan_search(c, 1, k, nullptr, 0);  // pipelined: two single-query buffers, or the stream layouts
     const size_t chain = 2 * align_up(p1.workspace_bytes(1, kk), 256);
@@ -1469,6 +1534,75 @@ int wvg_search_device_check(wvg_ctx *ctx, void *d_workspace, void *stream)
     return fail(WVG_ERR_DEVICE, "device search status " + std::to_string(st));
 }
 
+// search_pipelined for a BQ corpus (the routes: bq_stream_route above).  d_queries are the raw float rows,
+// as wvg_search_device takes them; their sign codes are made on the device.
+static int search_pipelined_bq(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k, const QShareFilt *flt,
+                               uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (nq == 0 || k == 0) return WVG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    {
+        std::shared_lock<std::shared_mutex> lk(c->rw);
+        const SearchPlan p = plan_search(c, 1, k, nullptr, 0);
+        if (p.empty || (flt && flt->stride == 0)) {  // empty corpus / slab, or an empty window
+            WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));
+            return WVG_OK;
+        }
+        const wvg_stream_plan sp = bq_stream_plan(c, p, nq, k);
+        if (sp.shared_rows || flt) {
+            const uint32_t groups = bq_stream_groups(c, p, nq);
+            const BqStreamLayout l = bq_stream_layout(c, nq, k, groups);
+            if (!d_workspace || workspace_bytes < l.total) return fail(WVG_ERR_INVALID, "workspace too small");
+            char *w = (char *)d_workspace;
+            uint64_t *partials = (uint64_t *)(w + l.partials), *qcodes = (uint64_t *)(w + l.qcodes);
+            uint64_t *codes = (uint64_t *)(w + l.codes);
+            // sign bits (CH/binary_quantization.go:32-45) at the scan's query pitch, as wvg_search_device
+            const uint32_t words = bq_words(c->dim), qpitch = bq_chunks(c->dim) * 2;
+            WVG_HIP(launch_bq_encode_rows(d_queries, nq, c->dim, 0, codes, s));
+            WVG_HIP(hipMemsetAsync(qcodes, 0, (size_t)nq * qpitch * 8, s));
+            WVG_HIP(hipMemcpy2DAsync(qcodes, (size_t)qpitch * 8, codes, (size_t)words * 8, (size_t)words * 8, nq,
+                                     hipMemcpyDeviceToDevice, s));
+            ProfArm arm(c->ctx);
+            if (arm.rc) return arm.rc;
+            if (sp.shared_rows) {  // every code read once per pass
+                BQShareArgs a{};
+                a.data = c->d_data;
+                a.valid = c->d_valid;
+                a.queries = qcodes;
+                a.partials = partials;
+                if (flt) {
+                    a.allow = flt->allow;
+                    a.allow_stride = flt->stride;
+                    a.allow_t0 = flt->t0;
+                }
+                a.tile_begin = p.tb;
+                a.tile_end = p.te;
+                a.nchunks = c->nchunks;
+                a.qpitch = qpitch;
+                a.nq = nq;
+                a.k = k;
+                a.reverse = next_direction(c, sp.passes);  // one direction per pass
+                a.plain = (uint32_t)bq_stream_plain(c, p.tb, p.te);
+                WVG_HIP(launch_scan_bq_qshare(a, groups, s));
+            } else {  // allow lists without the shared-row scan: K5 takes one window, so one launch per query
+                for (uint32_t i = 0; i < nq; i++) {
+                    ScanArgs a = scan_args_for(c, qcodes + (size_t)i * qpitch, qpitch, 1, k, nullptr, p.tb, p.te);
+                    a.allow = flt->allow + (size_t)i * flt->stride;
+                    a.allow_words = flt->stride;
+                    a.allow_t0 = flt->t0;
+                    WVG_HIP(launch_scan_bq(a, partials + (size_t)i * groups * k, (int)groups, s));
+                }
+            }
+            WVG_HIP(launch_merge_lists(partials, nq, groups, k, k, c->id_base, d_ids, d_dists, d_counts, s));
+            return WVG_OK;
+        }
+    }
+    // one query, or one full scan per query, without allow lists: wvg_search_device's own route
+    // (it plans and locks for itself; its layout is part of wvg_search_workspace_size)
+    return wvg_search_device(c, d_queries, nq, k, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
+}
+
 // wvg_search_device_pipelined and wvg_search_device_pipelined_filtered.  flt: null = no filter; otherwise
 // the caller's per-query allow words on the device (QShareFilt: never read by the host, so the scanned
 // tile range is the corpus's own and the kernels apply the window).
@@ -1478,7 +1612,9 @@ static int search_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, 
 {
     if (!c) return fail(WVG_ERR_INVALID, "null corpus");
     if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "k above 256 is not supported by the fused top-k");
-    if (c->kind != WVG_KIND_F32) return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32 corpora");
+    if (c->kind == WVG_KIND_BQ)
+        return search_pipelined_bq(c, d_queries, nq, k, flt, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
+    if (c->kind != WVG_KIND_F32) return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32 and BQ corpora");
     if (c->dim % 4 != 0) return fail(WVG_ERR_UNSUPPORTED, "device search needs dim % 4 == 0");
     if (nq == 0 || k == 0) return WVG_OK;
     hipStream_t s = (hipStream_t)stream;

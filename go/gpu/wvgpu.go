@@ -956,8 +956,12 @@ func (x *Corpus) SearchDevice(b DeviceBuffers, nq, k int) error {
 }
 
 // SearchDevicePipelined: nq single-query scans in one query-stream launch.
-// F32 and BQ corpora (BQ: b.Queries are the raw float rows; per query the Hamming
-// top-k, (distance, docID)-ordered, the queries sharing each read of the codes).
+// F32, BQ and PQ corpora (BQ: b.Queries are the raw float rows; per query the Hamming
+// top-k, (distance, docID)-ordered, the queries sharing each read of the codes.
+// PQ: the raw float rows too; the LUTs are made on the device and 4 or 2 queries
+// share each read of the codes and each lookup where that many LUTs fit LDS; per
+// query the ADC top-k of SearchDevice.  A PQ corpus without a codebook is
+// unsupported).
 func (x *Corpus) SearchDevicePipelined(b DeviceBuffers, nq, k int) error {
 	defer pin(x)()
 	return err(C.wvg_search_device_pipelined(x.h, (*C.float)(b.Queries), C.uint32_t(nq), C.uint32_t(k),
@@ -976,8 +980,10 @@ type StreamPlan struct {
 }
 
 // DevicePipelinedPlan: the StreamPlan of a call with nq queries and k results
-// each.  Host only: nothing is launched.  F32 and BQ corpora (BQ: 8 queries per
-// pass for nq >= 2 with cache_reuse on, never seeded or screened).
+// each.  Host only: nothing is launched.  F32, BQ and PQ corpora (BQ: 8 queries per
+// pass for nq >= 2 with cache_reuse on, never seeded or screened; PQ: 4 per pass up
+// to m = 32 at ks = 256, 2 up to m = 64, one scan per query beyond; a PQ corpus
+// without a codebook is unsupported).
 func (x *Corpus) DevicePipelinedPlan(nq, k int) (StreamPlan, error) {
 	defer pin(x)()
 	if nq < 0 || k < 0 {
@@ -1066,7 +1072,7 @@ func (c *Ctx) CopyWordsToDevice(dst unsafe.Pointer, src []uint64, s unsafe.Point
 
 // SearchDevicePipelinedFiltered: SearchDevicePipelined with one allow list per
 // query (a `where` filter's AllowList, V/flat/index.go:423-449), read on the
-// device: per query the results of Search with that list.  F32 and BQ corpora.
+// device: per query the results of Search with that list.  F32, BQ and PQ corpora.
 func (x *Corpus) SearchDevicePipelinedFiltered(b DeviceBuffers, nq, k int, allow DeviceAllow) error {
 	defer pin(x)()
 	if nq < 0 || k < 0 {

@@ -335,10 +335,11 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * UINT64_MAX, dists +inf, counts 0 (as wvg_search).  wvg_search_device
  * takes F32, BQ and PQ corpora (d_queries: float [nq][dim]; BQ codes and PQ
  * LUTs are built on the device -- size the workspace after the PQ codebook
- * is set); wvg_search_device_pipelined takes F32 and BQ corpora.  For a BQ
- * corpus the size is the largest of wvg_search_device's layout and the
- * pipelined ones (status block, partial lists [nq][row ranges][k], the
- * queries' codes); it never got smaller than it was.                       */
+ * is set); wvg_search_device_pipelined takes the same three kinds.  For a BQ
+ * corpus, and for a PQ corpus with a codebook, the size is the largest of
+ * wvg_search_device's layout and the pipelined ones (status block, partial
+ * lists [nq][row ranges][k], the queries' codes or LUTs); it never got
+ * smaller than it was.                                                     */
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k);
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                       uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
@@ -375,6 +376,22 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
  * lexicographic top-k, ascending.  The order the reference's heap keeps
  * inside ties is what wvg_search_bq_candidates returns, and that needs the
  * host; the rescore of the candidates stays with wvg_rescore or the caller.
+ * PQ corpora (d_queries: float [nq][dim], as wvg_search_device takes them;
+ * the LUTs are made on the device): with nq >= 2, cache_reuse on and a
+ * codebook of which at least two LUTs (m x ks x 4 bytes each) fit one
+ * workgroup's LDS, three launches on `stream`: the LUTs, a scan whose waves
+ * load every 64-row tile of codes once per pass of Q queries -- Q = 4 where
+ * four LUTs fit (m <= 32 at ks = 256), else 2 (m <= 64) -- and look each
+ * (row, segment) up once for all of them in an LDS image that keeps the Q
+ * queries' entries side by side, then the merge of the partial lists; no
+ * workgroup waits for another and the status block is not touched.  Every
+ * query's sum runs in segment order from 0, so per query the result is
+ * wvg_search_device's for that query alone, bit for bit.  One query,
+ * cache_reuse = 0 or a larger codebook (m >= 96 at ks = 256) is
+ * wvg_search_device's route for that nq.  A PQ corpus whose codebook has not
+ * been set has no (m, ks) and hence no route: WVG_ERR_UNSUPPORTED from this
+ * call, the filtered one and the plan, checked before anything else about
+ * the corpus (wvg_search_device answers WVG_ERR_INVALID, as before).
  * wvg_search_device_pipelined_plan tells which route a call takes.          */
 int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                                 uint64_t *d_ids, float *d_dists, uint32_t *d_counts,
@@ -404,7 +421,11 @@ int wvg_search_device_pipelined(wvg_corpus *c, const float *d_queries, uint32_t 
  * the shared-row BQ scan masks each query's rows with its own words and does
  * not load a tile no query of the pass allows; with one query or cache_reuse
  * = 0, one Hamming scan launch per query, each with its window, and one
- * merge.  Otherwise as wvg_search_device_pipelined: F32 and BQ corpora,
+ * merge.  PQ corpora: the shared-row PQ scan does the same with its Q
+ * queries per pass; where it does not apply (one query, cache_reuse = 0, a
+ * codebook beyond it), one ADC scan launch per query, each with its window,
+ * and one merge.  Otherwise as wvg_search_device_pipelined: F32, BQ and PQ
+ * corpora (a PQ corpus without a codebook: WVG_ERR_UNSUPPORTED),
  * asynchronous on `stream`, no allocation, no host synchronization,
  * capturable; the same workspace rule.                                      */
 int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
@@ -418,8 +439,12 @@ int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, 
  * With an allow list the same call shares rows under the same conditions.
  * nq == 0, k == 0 or an empty corpus: passes = 0.  A BQ corpus: {1, Q,
  * ceil(nq / Q), 0, 0} with the scan's Q (8) for nq >= 2 and cache_reuse on,
- * {0, 1, nq, 0, 0} otherwise.  Errors as the search's (k > 256, a PQ corpus,
- * an F32 corpus with dim % 4 != 0).                                         */
+ * {0, 1, nq, 0, 0} otherwise.  A PQ corpus: {1, Q, ceil(nq / Q), 0, 0} with
+ * the scan's Q (4 or 2 by how many of its LUTs fit LDS for this k) for nq
+ * >= 2 and cache_reuse on, {0, 1, nq, 0, 0} otherwise, a codebook beyond
+ * the shared scan (m >= 96 at ks = 256) included.  Errors as the search's
+ * (a PQ corpus without a codebook, k > 256, an F32 corpus with dim % 4 !=
+ * 0).                                                                       */
 typedef struct wvg_stream_plan {
     uint32_t shared_rows;      /* 1: the shared-row kernel; 0: one scan per query */
     uint32_t queries_per_pass; /* queries that share one read of the rows (1 if !shared_rows) */

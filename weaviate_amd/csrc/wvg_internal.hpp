@@ -491,6 +491,32 @@ struct BQShareArgs {
 uint32_t bq_qshare_queries_per_pass(uint32_t nchunks, uint32_t k);
 uint32_t bq_qshare_groups(uint64_t ntiles, int num_cus);
 hipError_t launch_scan_bq_qshare(const BQShareArgs &a, uint32_t groups, hipStream_t s);
+// Shared-row query stream of a PQ corpus (scan_pq_qshare_kernel, wvg_pq_qshare.hip): one launch of
+// (groups, passes) 16-wave workgroups; pass p scores queries [p Q, min(nq, (p + 1) Q)), Q =
+// pq_qshare_queries_per_pass(), against every tile of its range, each tile loaded once, in direction
+// (reverse + p) & 1, and leaves one k-list per (query, range) in partials [nq][groups][k].  The
+// workgroup's LDS image holds the pass's Q LUTs with the Q queries' entries of one (segment, code)
+// side by side, so one LDS read per (row, segment) serves the pass.  The caller merges the lists
+// (launch_merge_lists) by stream order.  allow: as BQShareArgs.
+constexpr int PQ_QSHARE_WAVES = 16;
+struct PQShareArgs {
+    const void *data;          // tiled codes
+    const uint64_t *valid;     // one word per tile
+    const float *luts;         // [nq][lpitch] launch_pq_lut's output, lut[s][c] at s * ks + c
+    uint64_t *partials;
+    const uint64_t *allow;
+    uint64_t allow_stride, allow_t0;
+    uint64_t tile_begin, tile_end;
+    uint32_t nchunks, lpitch, nq, k;
+    uint32_t m, ks;
+    int metric;
+    uint32_t reverse;          // direction of pass 0
+    uint32_t plain;            // code loads with the default cache policy instead of non-temporal
+};
+// 4 or 2 where that many LUTs fit one workgroup's LDS, else 1: no shared scan for this (m, ks, k).
+uint32_t pq_qshare_queries_per_pass(uint32_t m, uint32_t ks, uint32_t k);
+uint32_t pq_qshare_groups(uint64_t ntiles, int num_cus);
+hipError_t launch_scan_pq_qshare(const PQShareArgs &a, uint32_t groups, hipStream_t s);
 // Heap replay (wvg_replay.hip).  prefix: per query, thr[q][g] = the k-th smallest
 // distance of ranges 0..g-1's lists (partials [nq][groups][k], ascending; +inf
 // while fewer than k rows precede range g).  filter: each wave's emitted keys

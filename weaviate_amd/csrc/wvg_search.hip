@@ -1424,18 +1424,71 @@ static int bq_stream_plain(const wvg_corpus *c, uint64_t tb, uint64_t te)
     return (te - tb) * (uint64_t)c->nchunks * 1024ull <= (800ull << 20);
 }
 
+// ---- PQ corpora in the pipelined search ----------------------------------------------------------
+// Two or more queries in a context with cache_reuse on, over a codebook whose LUTs fit LDS at least
+// two at a time (pq_qshare_queries_per_pass), take the shared-row PQ scan (scan_pq_qshare_kernel,
+// wvg_pq_qshare.hip) and the list merge: the LUT launch and those two on the caller's stream.  One
+// query, cache_reuse = 0 or a larger codebook is wvg_search_device's route for that nq; with allow
+// lists one launch_scan_pq per query, each with its own window, then one merge.  Results are the
+// (ADC distance, docID)-lexicographic top-k on every route.  A PQ corpus without a codebook has no
+// (m, ks) and hence no route: WVG_ERR_UNSUPPORTED from the three pipelined entry points.
+static bool pq_stream_route(const wvg_corpus *c, uint32_t nq, uint32_t k)
+{
+    if (tuning().qshare < 0) return false;
+    return nq >= 2 && c->kind == WVG_KIND_PQ && c->ctx->opt.cache_reuse &&
+           pq_qshare_queries_per_pass(c->pq_m, c->pq_ks, k) >= 2;
+}
+
+static wvg_stream_plan pq_stream_plan(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k)
+{
+    wvg_stream_plan sp{0u, 1u, p1.empty ? 0u : nq, 0u, 0u};
+    if (p1.empty || !pq_stream_route(c, nq, k)) return sp;
+    sp.shared_rows = 1;
+    sp.queries_per_pass = pq_qshare_queries_per_pass(c->pq_m, c->pq_ks, k);
+    sp.passes = (nq + sp.queries_per_pass - 1) / sp.queries_per_pass;
+    return sp;
+}
+
+// Workspace of a pipelined PQ call (after the status block): partial lists [nq][groups][k], then the
+// queries' LUTs [nq][m ks].
+struct PqStreamLayout {
+    size_t partials = 0, luts = 0, total = 0;
+};
+static PqStreamLayout pq_stream_layout(const wvg_corpus *c, uint32_t nq, uint32_t k, uint32_t groups)
+{
+    PqStreamLayout l;
+    l.partials = WS_STATUS_BYTES;
+    l.luts = l.partials + align_up((size_t)nq * groups * k * 8, 256);
+    l.total = l.luts + align_up((size_t)nq * c->pq_m * c->pq_ks * 4, 256);
+    return l;
+}
+
+// Shared-row code loads, as bq_stream_plain: the default policy while the codes are within a few
+// times the Infinity Cache (the next pass walks the other way), non-temporal beyond.
+static int pq_stream_plain(const wvg_corpus *c, uint64_t tb, uint64_t te)
+{
+    if (tuning().k1_loads) return plain_loads(c, tb, te);
+    return (te - tb) * (uint64_t)c->nchunks * 1024ull <= (800ull << 20);
+}
+
 int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg_stream_plan *out)
 {
     if (!c || !out) return fail(WVG_ERR_INVALID, "null corpus / plan");
+    if (c->kind == WVG_KIND_PQ && !c->d_centers)
+        return fail(WVG_ERR_UNSUPPORTED, "pipelined search of a PQ corpus needs its codebook");
     if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "k above 256 is not supported by the fused top-k");
-    if (c->kind != WVG_KIND_F32 && c->kind != WVG_KIND_BQ)
-        return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32 and BQ corpora");
+    if (c->kind != WVG_KIND_F32 && c->kind != WVG_KIND_BQ && c->kind != WVG_KIND_PQ)
+        return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32, BQ and PQ corpora");
     if (c->kind == WVG_KIND_F32 && c->dim % 4 != 0) return fail(WVG_ERR_UNSUPPORTED, "device search needs dim % 4 == 0");
     *out = wvg_stream_plan{0u, 1u, 0u, 0u, 0u};
     if (nq == 0 || k == 0) return WVG_OK;
     std::shared_lock<std::shared_mutex> lk(c->rw);
     if (c->kind == WVG_KIND_BQ) {
         *out = bq_stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k);
+        return WVG_OK;
+    }
+    if (c->kind == WVG_KIND_PQ) {
+        *out = pq_stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k);
         return WVG_OK;
     }
     uint32_t seed_tiles;
@@ -1475,6 +1528,12 @@ size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
         const SearchPlan pb = plan_search(c, 1, k, nullptr, 0);
         const size_t shared = bq_stream_layout(c, nq, kk, bq_qshare_groups(pb.te - pb.tb, c->ctx->num_cus)).total;
         const size_t single = bq_stream_layout(c, nq, kk, (uint32_t)pb.groups).total;
+        return std::max({dev, shared, single});
+    }
+    if (c->kind == WVG_KIND_PQ && c->d_centers) {  // pipelined: the shared-row layout, or the per-query launches'
+        const SearchPlan pb = plan_search(c, 1, k, nullptr, 0);
+        const size_t shared = pq_stream_layout(c, nq, kk, pq_qshare_groups(pb.te - pb.tb, c->ctx->num_cus)).total;
+        const size_t single = pq_stream_layout(c, nq, kk, (uint32_t)pb.groups).total;
         return std::max({dev, shared, single});
     }
     if (c->kind != WVG_KIND_F32) return dev;  // no pipelined mode
@@ -1603,6 +1662,77 @@ static int search_pipelined_bq(wvg_corpus *c, const float *d_queries, uint32_t n
     return wvg_search_device(c, d_queries, nq, k, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
 }
 
+// search_pipelined for a PQ corpus with a codebook (the routes: pq_stream_route above).  d_queries are the
+// raw float rows, as wvg_search_device takes them; their LUTs are made on the device.
+static int search_pipelined_pq(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k, const QShareFilt *flt,
+                               uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
+                               size_t workspace_bytes, void *stream)
+{
+    if (nq == 0 || k == 0) return WVG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    {
+        std::shared_lock<std::shared_mutex> lk(c->rw);
+        const SearchPlan p = plan_search(c, 1, k, nullptr, 0);
+        if (p.empty || (flt && flt->stride == 0)) {  // empty corpus / slab, or an empty window
+            WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));
+            return WVG_OK;
+        }
+        const wvg_stream_plan sp = pq_stream_plan(c, p, nq, k);
+        if (sp.shared_rows || flt) {
+            const uint32_t groups = sp.shared_rows ? pq_qshare_groups(p.te - p.tb, c->ctx->num_cus) : (uint32_t)p.groups;
+            const PqStreamLayout l = pq_stream_layout(c, nq, k, groups);
+            if (!d_workspace || workspace_bytes < l.total) return fail(WVG_ERR_INVALID, "workspace too small");
+            char *w = (char *)d_workspace;
+            uint64_t *partials = (uint64_t *)(w + l.partials);
+            float *luts = (float *)(w + l.luts);
+            const uint32_t lpitch = c->pq_m * c->pq_ks;
+            // the queries' LUTs (CH/product_quantization.go:329-337), as wvg_search_device
+            WVG_HIP(launch_pq_lut(c->metric, d_queries, nq, c->dim, c->d_centers, c->pq_m, c->pq_ks, c->pq_ds, luts, s));
+            ProfArm arm(c->ctx);
+            if (arm.rc) return arm.rc;
+            if (sp.shared_rows) {  // every code read once per pass
+                PQShareArgs a{};
+                a.data = c->d_data;
+                a.valid = c->d_valid;
+                a.luts = luts;
+                a.partials = partials;
+                if (flt) {
+                    a.allow = flt->allow;
+                    a.allow_stride = flt->stride;
+                    a.allow_t0 = flt->t0;
+                }
+                a.tile_begin = p.tb;
+                a.tile_end = p.te;
+                a.nchunks = c->nchunks;
+                a.lpitch = lpitch;
+                a.nq = nq;
+                a.k = k;
+                a.m = c->pq_m;
+                a.ks = c->pq_ks;
+                a.metric = c->metric;
+                a.reverse = next_direction(c, sp.passes);  // one direction per pass
+                a.plain = (uint32_t)pq_stream_plain(c, p.tb, p.te);
+                WVG_HIP(launch_scan_pq_qshare(a, groups, s));
+            } else {  // allow lists without the shared-row scan: K8 takes one window, so one launch per query
+                for (uint32_t i = 0; i < nq; i++) {
+                    ScanArgs a = scan_args_for(c, luts + (size_t)i * lpitch, lpitch, 1, k, nullptr, p.tb, p.te);
+                    a.allow = flt->allow + (size_t)i * flt->stride;
+                    a.allow_words = flt->stride;
+                    a.allow_t0 = flt->t0;
+                    a.dense = 0;  // (the dense forms are for scans without an allow list)
+                    WVG_HIP(launch_scan_pq(a, partials + (size_t)i * groups * k, (int)groups, s));
+                }
+            }
+            WVG_HIP(launch_merge_lists(partials, nq, groups, k, k, c->id_base, d_ids, d_dists, d_counts, s));
+            return WVG_OK;
+        }
+    }
+    // one query, one full scan per query or a codebook beyond the shared scan, without allow lists:
+    // wvg_search_device's own route (it plans and locks for itself; its layout is part of
+    // wvg_search_workspace_size)
+    return wvg_search_device(c, d_queries, nq, k, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
+}
+
 // wvg_search_device_pipelined and wvg_search_device_pipelined_filtered.  flt: null = no filter; otherwise
 // the caller's per-query allow words on the device (QShareFilt: never read by the host, so the scanned
 // tile range is the corpus's own and the kernels apply the window).
@@ -1611,10 +1741,14 @@ static int search_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, 
                             size_t workspace_bytes, void *stream)
 {
     if (!c) return fail(WVG_ERR_INVALID, "null corpus");
+    if (c->kind == WVG_KIND_PQ && !c->d_centers)
+        return fail(WVG_ERR_UNSUPPORTED, "pipelined search of a PQ corpus needs its codebook");
     if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "k above 256 is not supported by the fused top-k");
     if (c->kind == WVG_KIND_BQ)
         return search_pipelined_bq(c, d_queries, nq, k, flt, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
-    if (c->kind != WVG_KIND_F32) return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32 and BQ corpora");
+    if (c->kind == WVG_KIND_PQ)
+        return search_pipelined_pq(c, d_queries, nq, k, flt, d_ids, d_dists, d_counts, d_workspace, workspace_bytes, stream);
+    if (c->kind != WVG_KIND_F32) return fail(WVG_ERR_UNSUPPORTED, "pipelined search supports F32, BQ and PQ corpora");
     if (c->dim % 4 != 0) return fail(WVG_ERR_UNSUPPORTED, "device search needs dim % 4 == 0");
     if (nq == 0 || k == 0) return WVG_OK;
     hipStream_t s = (hipStream_t)stream;

@@ -240,7 +240,8 @@ class Corpus:
                                 d_workspace: int, workspace_bytes: int, stream: int = 0, d_allow: int = 0,
                                 allow_stride: int = 0, allow_first_id: int = 0) -> None:
         """wvg_search_device_pipelined on device pointers, asynchronous on `stream`; with d_allow (device
-        words [nq][allow_stride], see allow_window) wvg_search_device_pipelined_filtered."""
+        words [nq][allow_stride], see allow_window) wvg_search_device_pipelined_filtered.  F32, BQ and PQ
+        corpora (d_queries: the float rows; a PQ corpus needs its codebook)."""
         if not d_allow:
             check(self.lib.wvg_search_device_pipelined(self.handle, d_queries, nq, k, d_ids, d_dists, d_counts,
                                                        d_workspace, workspace_bytes, stream))

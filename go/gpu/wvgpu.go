@@ -997,6 +997,23 @@ func (x *Corpus) DevicePipelinedPlan(nq, k int) (StreamPlan, error) {
 		Passes: int(sp.passes), Seeded: sp.seeded != 0, Screened: sp.screened != 0}, nil
 }
 
+// DevicePipelinedShadow: whether the next SearchDevicePipelined(nq, k) call outside
+// a stream capture reads the corpus's bf16 shadow (a screened call in a context
+// with BatchScreen != 0), and the bytes per row of capacity the first such call
+// allocates (it also builds the shadow with one pass over the rows); 0 when it
+// does not.  Results are the same bits either way.  Host only.
+func (x *Corpus) DevicePipelinedShadow(nq, k int) (readsShadow bool, shadowBytesPerRow int, e error) {
+	defer pin(x)()
+	if nq < 0 || k < 0 {
+		return false, 0, errors.New("wvgpu: negative nq or k")
+	}
+	var rs, bpr C.uint32_t
+	if e := err(C.wvg_search_device_pipelined_shadow(x.h, C.uint32_t(nq), C.uint32_t(k), &rs, &bpr)); e != nil {
+		return false, 0, e
+	}
+	return rs != 0, int(bpr), nil
+}
+
 // BatchPlan tells the route a batch of queries takes on a corpus (struct
 // wvg_batch_plan).  Results are identical on every route.
 type BatchPlan struct {

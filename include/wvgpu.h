@@ -453,6 +453,27 @@ typedef struct wvg_stream_plan {
     uint32_t screened;         /* the bf16 screen runs */
 } wvg_stream_plan;
 int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg_stream_plan *out);
+/* Whether the next wvg_search_device_pipelined(c, ..., nq, k, ...) call outside a
+ * stream capture reads the corpus's bf16 shadow, and what that costs in memory.
+ * A screened call (wvg_stream_plan.screened: l2-squared, d = 128, k <= 64, a
+ * seeded range) in a context with batch_screen != 0 screens every 64-row tile
+ * from the shadow that l2-squared batches use (2 * dim + 4 bytes per row) and
+ * reads fp32 values only for the rows the screen admits; results are the same
+ * bits either way.  *reads_shadow = 1 then, and *shadow_bytes_per_row = what
+ * the first such call allocates per row of capacity (0 with *reads_shadow = 0).
+ * Two facts for the caller: the FIRST such call of a corpus allocates the
+ * shadow and builds it with one pass over the rows on the call's stream (a
+ * benchmark pays that in its warm-up), and rows written since are rebuilt at
+ * the next call, as for batches; the shadow is dropped when the corpus grows.
+ * batch_screen = 0 keeps the stream off the shadow as it keeps batches off it.
+ * Under stream capture nothing is allocated or built: a captured call records
+ * the shadow-fed kernel if the shadow exists and is current, and the
+ * fp32-screened kernel otherwise, as it does after a failed allocation.
+ * Unscreened calls (other metrics or dims, k > 64, one query, cache_reuse = 0,
+ * long unseeded ranges) never allocate a shadow.  The workspace size does not
+ * depend on any of this.  Host only; either pointer may be NULL.             */
+int wvg_search_device_pipelined_shadow(wvg_corpus *c, uint32_t nq, uint32_t k, uint32_t *reads_shadow,
+                                       uint32_t *shadow_bytes_per_row);
 /* The route a batch of nq queries with this k takes on corpus c (wvg_search,
  * wvg_search_device, wvg_multi_search), for a caller that sizes its batches
  * or wants to see the route: results are identical on every route by design.

@@ -112,6 +112,7 @@ SIGNATURES = {
                                                      c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                                      c_void_p]),
     "wvg_search_device_pipelined_plan": (c_int, [c_void_p, c_uint32, c_uint32, _P(StreamPlan)]),
+    "wvg_search_device_pipelined_shadow": (c_int, [c_void_p, c_uint32, c_uint32, _P(c_uint32), _P(c_uint32)]),
     "wvg_search_batch_plan": (c_int, [c_void_p, c_uint32, c_uint32, c_int, _P(BatchPlan)]),
     "wvg_topk_merge_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -592,6 +592,9 @@ int wvgx_set_tuning(int key, int value)
     } else if (key == 41 && value >= 1) {
         old = t.qshare_seed_share;
         t.qshare_seed_share = value;
+    } else if (key == 42) {
+        old = t.qshare_shadow;
+        t.qshare_shadow = value;
     }
     return old;
 }

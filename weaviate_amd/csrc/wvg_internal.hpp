@@ -380,9 +380,15 @@ struct QShareArgs {
     uint64_t *seeds;         // [nq] sample k-th keys, written by the prologue
     uint32_t seed_tiles;     // tiles of the sample (0 = none: open bounds)
     uint32_t seq_combine;    // tools A/B: one group_combine_publish per query instead of the pass's batched combine
-    uint32_t screen;         // 1 = the screened scan (qshare_screened): the prologue writes qbf and qconst
+    uint32_t screen;         // 1 = the screened scan (qshare_screened): the prologue writes qbf and qconst;
+                             // 2 = the screened scan fed from the corpus's bf16 shadow (scan_f32_qshare_shadow_kernel)
     uint16_t *qbf;           // [nq][128] the queries as bf16 (round to nearest), written by the prologue
+                             // (screen = 2: [ceil(nq / 16)][4][64] 16-B fragments, screen_qfrag_kernel's lane layout)
     float4 *qconst;          // [nq] {Nq2, K1q, K2q, Cq = Nq2 - K2q}: the screen's bound (wvg_qshare.hip)
+                             // (screen = 2: {K1, K2, Cq, 0}, K3c-L2's constants, screen_l2_query_consts)
+    const void *shadow;      // screen = 2: the corpus's bf16 shadow [tile][4 k-blocks][4 row groups][64] x 16 B
+    const float *norms;      // screen = 2: its row-norm upper bounds [tile][64]
+    float hg;                // screen = 2: K3c-L2's (1 - g) / 2 (screen_l2_hg)
     uint64_t *screen_count;  // tools build, two words per launch: [0] (query, tile) pairs with an admitted row (low
                              // half) and all (query, tile) pairs (high half); [1] admitted (query, row) pairs (low
                              // half) and rounds of the exact chain (high half)
@@ -556,6 +562,36 @@ constexpr int SCREEN_M = 16;  // lower bounds kept per (wave, query) and per (ro
 // (K3c-L2 only, which takes any count) has exactly dim / 32, so its shadow is 2 * dim + 4 bytes per row
 inline uint32_t screen_kblocks(uint32_t dim, bool l2 = false) { return l2 ? (dim + 31) / 32 : (dim + 63) / 64 * 2; }
 bool screen_supported(uint32_t dim, int metric, uint32_t k);
+// An upper bound of the L2 norm from the exact square sum in double:
+// rounded up past the float cast; +inf for a non-finite row.
+__device__ __forceinline__ float norm_upper(double ss)
+{
+    if (!(ss < 1e300)) return __builtin_inff();  // inf / NaN components
+    return (float)(__builtin_sqrt(ss) * (1.0 + 1e-6));
+}
+// K3c-L2's constants (wvg_screen.hip, "K3c-L2"): alpha, the rows' hg = (1 - g) / 2 rounded down, and a
+// query's K1 / K2 (the dot's) and Cq <= |q|^2 - alpha Nq^2 - 2^-100 from its fp64 square sum ss, rounded to
+// the safe side.  A query whose norm bound is above 2^56 or not finite: K1 = +inf, Cq = -inf (no row skipped).
+// The batched screen (screen_qconst_l2_kernel) and the shared-row scan's prologue (wvg_qshare.hip) both
+// take them from here.
+__device__ __host__ inline double screen_l2_alpha(uint32_t dim) { return ((double)dim / 16.0 + 32.0) * 0x1p-24; }
+inline float screen_l2_hg(uint32_t dim)
+{
+    return (float)((1.0 - (screen_l2_alpha(dim) + 0x1p-18)) * 0.5 * (1.0 - 0x1p-23));
+}
+__device__ __forceinline__ float screen_l2_query_consts(double ss, uint32_t dim, float &K1, float &K2, float &C)
+{
+    const float nq_up = norm_upper(ss);
+    const float c = 0x1p-7f + 0x1p-15f + (float)dim * 0x1p-21f;
+    K1 = c * nq_up + 0x1p-120f;
+    K2 = 0x1p-120f * nq_up + 0x1p-110f;
+    C = (float)(ss * (1.0 - 0x1p-19 - screen_l2_alpha(dim)) - 0x1p-100);
+    if (!(nq_up <= 0x1p56f)) {
+        K1 = __builtin_inff();
+        C = -__builtin_inff();
+    }
+    return nq_up;
+}
 uint32_t screen_row_ranges(uint32_t nq, uint64_t ntiles, int num_cus);
 #ifdef WVG_TOOLS
 void screen_counters(uint64_t out[4], bool reset);
@@ -722,6 +758,9 @@ struct Tuning {
     int qshare_screen = 1;   // (tuning key 40) 1 = seeded L2 d = 128 k <= 64 launches screen every tile with a bf16
                              // MFMA lower bound and fold only the admitted (query, tile) pairs; 0 = every pair
                              // folded (A/B; profiles/r12/qshare_screen/)
+    int qshare_shadow = 1;   // (tuning key 42) 1 = a screened shared-row launch reads the corpus's bf16 shadow and
+                             // gathers fp32 only for admitted rows (scan_f32_qshare_shadow_kernel) where the
+                             // shadow is there; 0 = always the fp32-screened kernel (A/B; profiles/r21/qshare_shadow/)
     int multi_bq_bound = 1;  // multi-GPU BQ heap flow (tuning key 36): 1 = the cross-slab bound X_s in the filter,
                              // 0 = every slab filters with its own thresholds only (A/B: rows replayed)
     int screen_diag = 0;     // K3d / K3i diagnostics (tuning key 18, tools build only): 4 = the fast check but no

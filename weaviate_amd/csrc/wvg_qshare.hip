@@ -212,6 +212,25 @@ __device__ __forceinline__ void screen_query_side(const QShareArgs &a, uint32_t 
                     : 0.0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    if (a.screen == 2) {
+        // The scan reads the corpus's shadow (qshare_shadow_body): the query as an MFMA fragment in
+        // screen_qfrag_kernel's layout -- fragment (q / 16, kb), lane l = query q % 16 at l & 15, elements
+        // 32 kb + 8 (l >> 4) .. + 7, so lane i < 16 of this wave converts elements 8 i .. 8 i + 7 (round to
+        // nearest even, as the rows') -- and K3c-L2's constants of the same fp64 square sum.
+        if (lane < QS_D / 8) {
+            const f4v lo = qj[2 * lane], hi = qj[2 * lane + 1];
+            const shortx4 blo = bf16_of(make_float4(lo.x, lo.y, lo.z, lo.w)), bhi = bf16_of(make_float4(hi.x, hi.y, hi.z, hi.w));
+            const uint2 wl = __builtin_bit_cast(uint2, blo), wh = __builtin_bit_cast(uint2, bhi);
+            reinterpret_cast<uint4 *>(a.qbf)[((size_t)(q >> 4) * 4 + (lane >> 2)) * 64 + (lane & 3) * 16 + (q & 15)] =
+                make_uint4(wl.x, wl.y, wh.x, wh.y);
+        }
+        if (lane == 0) {
+            float K1, K2, C;
+            screen_l2_query_consts(ss, QS_D, K1, K2, C);
+            a.qconst[q] = make_float4(K1, K2, C, 0.0f);
+        }
+        return;
+    }
     if (lane < QS_D / 4)
         reinterpret_cast<shortx4 *>(a.qbf)[(size_t)q * (QS_D / 4) + c] = bf16_of(make_float4(v.x, v.y, v.z, v.w));
     if (lane == 0) {
@@ -831,6 +850,292 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
     qshare_scan_body<WVG_M_L2, QS_D, 1, true, true, true>(a, f);
 }
 
+// The shadow-fed screened scan (scan_f32_qshare_shadow_kernel; QShareArgs::screen = 2).  The coverage,
+// grid, row ranges, serpentine, seeds, lists, combine and mergers are the screened form's.  What differs is
+// what a tile costs in memory: the fp32-screened kernel loads the lane's whole 512-byte row only to round
+// it to bf16 and sum its squares, and about 3 rows of 64 ever use their fp32 values.  A corpus that has a
+// bf16 shadow (shadow_frag_kernel's fragments and shadow_norm_kernel's norm bounds, kept current by
+// ensure_shadow) already holds both results, so a tile is 16 fragments of 1 KiB (one 16-byte load per lane
+// each, [kb 0..3][rg 0..3]) and 256 B of norms, and the fp32 values are gathered from a.data for admitted
+// (query, row) pairs only.
+//
+// The operands: v_mfma_f32_16x16x32_bf16 with A = the pass's query fragment of k-block kb (held in 16
+// registers for the pass), B = the tile's row fragment (kb, rg); four k-blocks chained into acc[rg].  The
+// result register r of lane l is the dot of query 4 (l >> 4) + r with row 16 rg + (l & 15): a lane holds
+// FOUR QUERIES x FOUR ROWS.  (Rows as A would give a lane one query and 16 rows: 16 norms and h terms per
+// lane instead of 4, against 12 constants instead of 3 -- about the same registers -- but a lane's 16 rows
+// x its query's allow word would need a per-lane 64-bit select of the 16 words; here the live mask of pair
+// (rg, r) is one scalar word per pair, built from the 16-bit fields of the validity / allow words.)
+// Admission bit 4 rg + r of the lane = that pair.
+//
+// The bound is K3c-L2's (wvg_screen.hip, "K3c-L2"), on exactly its operands: the stored fragments, the
+// stored norm bounds Nx, and K1 / K2 / Cq from screen_l2_query_consts:
+//   h = (Nx Nx) hg,  E1 = fma(Nx, K1q, K2q),  u = (s - h) + E1,  lower = max(Cq - 2 u, 0) <= r.
+// Two things carry over unchanged.  The accumulation: K3c-L2's s is one v_mfma_f32_16x16x32_bf16 chain
+// over the row's k-blocks in ascending order from a zero accumulator (screen_body's acc[mq][nr]), which is
+// what acc[rg] is here -- four k-blocks at d = 128; its (b) covers the bf16 operands and that fp32
+// accumulation whichever operand is A.  (a) is about r, the same AVX2-order chain (chunk_update2 is
+// chunk_update on pairs).  The special values: a row with Nx > 2^60 (inf: a NaN / inf row) gets h = NaN; a
+// query with Nq > 2^56 or not finite gets K1 = +inf, Cq = -inf; a NaN or infinite s makes u NaN or
+// infinite.  Each ends in lower = NaN (taken as -inf, sc_lower_l2's rule), -inf, 0 or +inf, and a pair is
+// skipped only if lower > tau_dist && lower < +inf with tau_dist NaN for an open tau: all of these admit.
+// Results do not depend on the bound's slack (the argument at the top of the file holds for any sound
+// bound): a pair that is not admitted holds no key below tau.
+//
+// The rounds are the screened form's with the row fetched on demand: a lane takes its lowest admitted pair
+// (rg, r), loads row 16 rg + (l & 15) of tile t from a.data -- 32 chunks 1 KiB apart, default policy, only
+// lanes that hold a pair -- and runs the unchanged chain against query 4 (l >> 4) + r from the fp32 LDS
+// image; the key is built from (t, row).  A pair belongs to exactly one lane, so keys stay unique; a lane
+// with two pairs on one row loads it twice (the second read hits cache).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+template <bool NT>
+__device__ __forceinline__ bf16x8 ld_frag(const uint4 *p)
+{
+    if constexpr (NT) return __builtin_bit_cast(bf16x8, __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p)));
+    else return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4 *>(p));
+}
+
+// Lanes (g, i) <- bit i of the 16-bit field rg of word[g]: the live rows 16 rg + i of a lane's pair.
+__device__ __forceinline__ uint64_t field16(uint64_t w, int rg) { return (w >> (16 * rg)) & 0xFFFFull; }
+
+template <bool FILT>
+__device__ __forceinline__ void qshare_shadow_body(const QShareArgs &a, const QShareFilt &f)
+{
+    constexpr int QP = 16, NC = QS_D / 4;
+    const uint32_t G = a.groups;
+    if (blockIdx.x >= G) {  // the mergers, as qshare_scan_body's
+        const uint32_t nm = gridDim.x - G;
+        for (uint32_t q = blockIdx.x - G; q < a.nq; q += nm) {
+            const bool got = merge_lists_ready<1, SCAN_WAVES>(
+                a.partials + (size_t)q * G * a.k, a.ready + (size_t)q * G, 1u, G, a.k, a.wait_limit, a.id_base,
+                a.ids ? a.ids + (size_t)q * a.k : nullptr, a.dists ? a.dists + (size_t)q * a.k : nullptr,
+                a.counts ? a.counts + q : nullptr, nullptr, 0u);
+            if (!got) {
+                if (threadIdx.x == 0) atomicOr(a.status, WVG_STATUS_MERGE_TIMEOUT);
+                fill_empty_body(a.ids, a.dists, a.counts, q, q + 1, a.k);
+            }
+            __syncthreads();
+        }
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const uint64_t ntiles = a.tile_end - a.tile_begin, total = (uint64_t)G * SCAN_WAVES;
+    const uint64_t gw = (uint64_t)blockIdx.x * SCAN_WAVES + wave_id();
+    const uint64_t t0 = a.tile_begin + ntiles * gw / total, t1 = a.tile_begin + ntiles * (gw + 1) / total;
+    const uint64_t n = t1 - t0;
+    const uint64_t split = a.cache_tail256 ? n - ((n * a.cache_tail256) >> 8) : (a.plain ? 0 : n);
+    const float4 *data = reinterpret_cast<const float4 *>(a.data);
+    const uint4 *shadow = reinterpret_cast<const uint4 *>(a.shadow);
+    cu64 *valid = (cu64 *)a.valid;
+    const uint32_t qstride = a.qpitch / 4;
+    const float hg = a.hg;
+    __shared__ f4v qfsh[QP * QS_FROW];  // the pass's fp32 queries (the rounds' operands)
+#ifdef WVG_TOOLS
+    uint32_t n_fold = 0, n_pairs = 0, n_rounds = 0, n_adm = 0;  // as qshare_scan_body's
+#endif
+    for (uint32_t q0 = 0, pass = 0; q0 < a.nq; q0 += QP, pass++) {
+        const uint32_t nqp = a.nq - q0 < (uint32_t)QP ? a.nq - q0 : (uint32_t)QP;
+        const bool rev = ((a.reverse + pass) & 1u) != 0;
+        cu64 *sd = (cu64 *)a.seeds + q0;
+        WaveTopK<1> tk[QP];
+#pragma unroll
+        for (int j = 0; j < QP; j++) tk[j].init_bounded((int)a.k, (uint32_t)j < nqp ? seed_bound(sd + j) : WVG_KEY_NONE);
+        {  // the fp32 queries into LDS, two chunks per thread: thread = (query, chunk), (query + QP / 2, chunk)
+            uint32_t tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            const f4v *srcf = reinterpret_cast<const f4v *>(a.queries) + (size_t)q0 * qstride;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const uint32_t fq = (tid >> 5) + h * (QP / 2), fc = tid & 31;
+                qfsh[fq * QS_FROW + fc] = fq < nqp ? srcf[(size_t)fq * qstride + fc] : f4v{0.0f, 0.0f, 0.0f, 0.0f};
+            }
+            __syncthreads();  // (the last pass's readers are past pass_combine_publish's barriers)
+        }
+        // the pass's query fragments and the lane's four queries' constants; a query past nqp is never
+        // admitted (its fragment column and constants may hold anything: an MFMA result depends on its own
+        // row and column only)
+        const uint32_t jg = (uint32_t)(lane >> 4) * 4;
+        bf16x8 qa[4];
+        float k1[4], k2[4], cq[4];
+        {
+            const uint4 *qf = reinterpret_cast<const uint4 *>(a.qbf) + (size_t)(q0 >> 4) * 4 * 64 + lane;
+#pragma unroll
+            for (int kb = 0; kb < 4; kb++) qa[kb] = ld_frag<false>(qf + kb * 64);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float4 c = jg + r < nqp ? a.qconst[q0 + jg + r] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                k1[r] = c.x;
+                k2[r] = c.y;
+                cq[r] = c.z;
+            }
+        }
+        uint64_t qlive[4];  // lanes whose query 4 (l >> 4) + r is one of the pass
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            qlive[r] = 0ull;
+#pragma unroll
+            for (int g = 0; g < 4; g++) qlive[r] |= (uint32_t)(4 * g + r) < nqp ? 0xFFFFull << (16 * g) : 0ull;
+        }
+        uint64_t m_next = n ? valid[rev ? t1 - 1 : t0] : 0ull;
+        cu64 *al = FILT ? (cu64 *)f.allow + (size_t)q0 * f.stride : nullptr;
+        uint64_t aw_next[FILT ? QP : 1], mq[FILT ? QP : 1];
+        if constexpr (FILT) {
+            if (n) pass_allow_words<QP>(aw_next, al, f.stride, f.t0, rev ? t1 - 1 : t0, nqp);
+        }
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint64_t t = rev ? t1 - 1 - i : t0 + i;
+            const uint64_t m = m_next;
+            uint64_t many = m;
+            if constexpr (FILT) {
+                many = 0ull;
+#pragma unroll
+                for (int j = 0; j < QP; j++) {
+                    mq[j] = m & aw_next[j];
+                    many |= mq[j];
+                }
+            }
+            if (i + 1 < n) {  // scalar prefetch of the next mask
+                m_next = valid[rev ? t - 1 : t + 1];
+                if constexpr (FILT) pass_allow_words<QP>(aw_next, al, f.stride, f.t0, rev ? t - 1 : t + 1, nqp);
+            }
+            if (many == 0ull) continue;  // wave-uniform: nothing live (FILT: and allowed) in this tile
+            const uint4 *sp = shadow + (size_t)t * (16 * 64) + lane;
+            bf16x8 xb[4][4];
+            if (i >= split) {
+#pragma unroll
+                for (int fr = 0; fr < 16; fr++) xb[fr >> 2][fr & 3] = ld_frag<false>(sp + fr * 64);
+            } else {
+#pragma unroll
+                for (int fr = 0; fr < 16; fr++) xb[fr >> 2][fr & 3] = ld_frag<true>(sp + fr * 64);
+            }
+            float nx[4];
+#pragma unroll
+            for (int rg = 0; rg < 4; rg++) nx[rg] = a.norms[(size_t)t * 64 + 16 * rg + (lane & 15)];
+            // tau of the lane's four queries, as a distance (NaN for an open tau)
+            float taud[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                uint32_t hi = (uint32_t)(tk[r].tau >> 32);
+#pragma unroll
+                for (int g = 1; g < 4; g++) hi = (lane >> 4) == g ? (uint32_t)(tk[4 * g + r].tau >> 32) : hi;
+                taud[r] = wvg_unord_f32(hi);
+            }
+            floatx4 acc[4];
+#pragma unroll
+            for (int rg = 0; rg < 4; rg++) acc[rg] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int kb = 0; kb < 4; kb++)
+#pragma unroll
+                for (int rg = 0; rg < 4; rg++)
+                    acc[rg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kb], xb[kb][rg], acc[rg], 0, 0, 0);
+            uint32_t adm = 0u;
+#pragma unroll
+            for (int rg = 0; rg < 4; rg++) {
+                const float nrm = nx[rg];
+                const float h = nrm <= 0x1p60f ? (nrm * nrm) * hg : __builtin_nanf("");
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    // the pair's live lanes: row 16 rg + i valid (FILT: and allowed by query 4 g + r), the query in the pass
+                    uint64_t live;
+                    if constexpr (FILT) {
+                        live = field16(mq[r], rg) | field16(mq[4 + r], rg) << 16 | field16(mq[8 + r], rg) << 32 |
+                               field16(mq[12 + r], rg) << 48;  // (mq[j] = 0 past nqp)
+                    } else {
+                        live = (field16(m, rg) * 0x0001000100010001ull) & qlive[r];
+                    }
+                    if (live == 0ull) continue;  // wave-uniform
+                    const float e1 = __builtin_fmaf(nrm, k1[r], k2[r]);
+                    const float u = (acc[rg][r] - h) + e1;
+                    float lower = cq[r] - 2.0f * u;
+                    lower = lower != lower ? -__builtin_inff() : __builtin_fmaxf(lower, 0.0f);
+                    const bool skip = (lower > taud[r] && lower < __builtin_inff()) || !__builtin_amdgcn_inverse_ballot_w64(live);
+                    adm |= skip ? 0u : 1u << (4 * rg + r);
+                }
+            }
+#ifdef WVG_TOOLS
+            n_pairs += nqp;
+            n_adm += (uint32_t)__builtin_popcount(adm);
+            {  // (query, tile) pairs with an admitted row: query 4 g + r over the lanes of group g
+                uint32_t any = 0u;
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const uint64_t b = __ballot((adm & (0x1111u << r)) != 0u);
+#pragma unroll
+                    for (int g = 0; g < 4; g++) any |= ((b >> (16 * g)) & 0xFFFFull) != 0ull ? 1u << (4 * g + r) : 0u;
+                }
+                n_fold += (uint32_t)__builtin_popcount(any);
+            }
+#endif
+            const float4 *tp = data + (size_t)t * NC * 64 + (lane & 15);
+            while (true) {
+                const uint64_t took_any = __ballot(adm != 0u);  // the lanes that score a pair in this round
+                if (took_any == 0ull) break;  // wave-uniform
+#ifdef WVG_TOOLS
+                n_rounds++;
+#endif
+                const bool has = adm != 0u;
+                const uint32_t b = has ? (uint32_t)__builtin_ctz(adm) : 0u;  // the lane's lowest admitted pair
+                adm &= adm - 1u;
+                const uint32_t jl = jg + (b & 3u), row = (b >> 2) * 16 + (uint32_t)(lane & 15);
+                uint64_t key = WVG_KEY_NONE;
+                if (has) {  // only lanes that hold a pair load
+                    const f4v *ql = qfsh + jl * QS_FROW;
+                    const float4 *xr = tp + (b >> 2) * 16;
+                    f2v c2[4][4];
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+#pragma unroll
+                        for (int p = 0; p < 4; p++) c2[r][p] = f2v{0.0f, 0.0f};
+                    // The row streams through a ring of RING chunks: the first RING requested before the chain
+                    // starts, chunk c + RING as chunk c is consumed.  (Written as xr[c] inside the chain the
+                    // loads came out one at a time, each waited for -- 32 memory latencies per round; the
+                    // whole row at once spills beside the lists.)
+                    constexpr int RING = 16;
+                    float4 x[RING];
+#pragma unroll
+                    for (int c = 0; c < RING; c++) x[c] = xr[(size_t)c * 64];
+#pragma unroll
+                    for (int c = 0; c < NC; c++) {
+                        chunk_update2<WVG_M_L2>(c2, c & 7, ql[c], x[c % RING]);
+                        if (c + RING < NC) x[c % RING] = xr[(size_t)(c + RING) * 64];
+                    }
+                    key =wvg_make_key(wrap_metric(a.metric, avx256_reduce2(c2)), (uint32_t)(t * 64 + row));
+                }
+#pragma unroll
+                for (int j = 0; j < QP; j++) {
+                    const uint64_t took = __ballot(has && jl == (uint32_t)j);
+                    if (took != 0ull)  // wave-uniform: some lane took query j in this round
+                        tk[j].offer_bounded(((took >> lane) & 1ull) ? key : WVG_KEY_NONE, [&] { return seed_bound(sd + j); });
+                }
+            }
+        }
+        pass_combine_publish<1, QP, true>(tk, nqp, a.k, a.partials, a.ready, (size_t)q0 * G + blockIdx.x, G, q0 + QP < a.nq);
+    }
+#ifdef WVG_TOOLS
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n_adm += __shfl_xor(n_adm, off);
+    if (lane == 0 && n_pairs) {
+        atomicAdd((unsigned long long *)a.screen_count, ((unsigned long long)n_pairs << 32) | n_fold);
+        atomicAdd((unsigned long long *)a.screen_count + 1, ((unsigned long long)n_rounds << 32) | n_adm);
+    }
+#endif
+}
+
+// (two waves per SIMD, as the screened form; profiles/r21/qshare_shadow/)
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_shadow_kernel(
+    QShareArgs a)
+{
+    qshare_shadow_body<false>(a, QShareFilt{});
+}
+
+__global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_f32_qshare_shadow_filt_kernel(
+    QShareArgs a, QShareFilt f)
+{
+    qshare_shadow_body<true>(a, f);
+}
+
 // Which corpora the kernel covers, its queries per pass and its grid.
 // (dim % 4: device search's own condition.  dim = 4 stays out: below 8 elements the reference returns the
 // scalar sum without the reduction tree, and a -0.0 sum would differ.)
@@ -941,6 +1246,14 @@ static hipError_t launch_qshare_e(const QShareArgs &a, uint32_t mergers, hipStre
     dim3 grid(a.groups + mergers), block(SCAN_WAVES * 64);
     if (a.screen) {
         if (METRIC != WVG_M_L2 || E != 1 || a.dim != QS_D || !a.qbf || !a.qconst) return hipErrorInvalidValue;
+        if (a.screen == 2) {  // fed from the corpus's shadow
+            if (!a.shadow || !a.norms) return hipErrorInvalidValue;
+            if (f)
+                launch_timed(scan_f32_qshare_shadow_filt_kernel, grid, block, 0, s, a, *f);
+            else
+                launch_timed(scan_f32_qshare_shadow_kernel, grid, block, 0, s, a);
+            return hipGetLastError();
+        }
         if (f)
             launch_timed(scan_f32_qshare_screen_filt_kernel, grid, block, 0, s, a, *f);
         else

@@ -109,14 +109,7 @@ __global__ __launch_bounds__(256) void shadow_frag_kernel(const float4 *__restri
     shadow[((t * kbn + kb) * 4 + rg) * 64 + lane] = *reinterpret_cast<const uint4 *>(&o);
 }
 
-// An upper bound of the L2 norm from the exact square sum in double:
-// rounded up past the float cast; +inf for a non-finite row.
-__device__ __forceinline__ float norm_upper(double ss)
-{
-    if (!(ss < 1e300)) return __builtin_inff();  // inf / NaN components
-    return (float)(__builtin_sqrt(ss) * (1.0 + 1e-6));
-}
-
+// (norm_upper, the rows' and queries' norm upper bound: wvg_internal.hpp)
 __global__ __launch_bounds__(256) void shadow_norm_kernel(const float4 *__restrict__ tiled, uint32_t nchunks,
                                                           uint64_t slot0, uint64_t n, float *norms, uint32_t *nmax)
 {
@@ -205,8 +198,7 @@ __global__ __launch_bounds__(256) void screen_qconst_kernel(const float *q, uint
 // |q|^2 - alpha Nq^2 - 2^-100 and Emax_q = E_tot at the corpus maximum norm,
 // from fp64 sums, rounded to the safe side.  A query whose norm bound is above
 // 2^56 or not finite: K1 = +inf, Cq = -inf (no fast rejection, every row a
-// candidate).
-__device__ __host__ inline double screen_l2_alpha(uint32_t dim) { return ((double)dim / 16.0 + 32.0) * 0x1p-24; }
+// candidate).  (screen_l2_alpha, screen_l2_query_consts: wvg_internal.hpp.)
 
 __global__ __launch_bounds__(256) void screen_qconst_l2_kernel(const float *q, uint32_t nq, uint32_t qpitch,
                                                                uint32_t dim, uint32_t nq_pad, const uint32_t *nmax,
@@ -224,16 +216,10 @@ __global__ __launch_bounds__(256) void screen_qconst_l2_kernel(const float *q, u
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
     if (lane) return;
-    const float nq_up = norm_upper(ss);
-    const float c = 0x1p-7f + 0x1p-15f + (float)dim * 0x1p-21f;
-    const double alpha = screen_l2_alpha(dim), beta = alpha + 0x1p-18;
+    float K1, K2, C;
+    const float nq_up = screen_l2_query_consts(ss, dim, K1, K2, C);
+    const double beta = screen_l2_alpha(dim) + 0x1p-18;
     const float nm = __uint_as_float(*nmax);
-    float K1 = c * nq_up + 0x1p-120f, K2 = 0x1p-120f * nq_up + 0x1p-110f;
-    float C = (float)(ss * (1.0 - 0x1p-19 - alpha) - 0x1p-100);
-    if (!(nq_up <= 0x1p56f)) {
-        K1 = __builtin_inff();
-        C = -__builtin_inff();
-    }
     const double e1 = __builtin_fmaf(nm, K1, K2);
     float E = (float)((2.0 * e1 + beta * ((double)nq_up * nq_up + (double)nm * nm) + 0x1p-99) * (1.0 + 0x1p-20));
     if (qi >= nq) K1 = K2 = C = E = 0.f;
@@ -2505,7 +2491,7 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
         (void)attr_l2;
     }
     // one launch of the chosen kernel over the ranges in x (K3c-L2 wraps x with Cq and hg)
-    const float hg = L.l2 ? (float)((1.0 - (screen_l2_alpha(L.dim) + 0x1p-18)) * 0.5 * (1.0 - 0x1p-23)) : 0.f;
+    const float hg = L.l2 ? screen_l2_hg(L.dim) : 0.f;
     auto launch = [&](const ScreenArgs &x, uint32_t blocks, hipEvent_t e0, hipEvent_t e1) {
         if (L.l2) {
             const ScreenL2Args xl{x, L.cq, hg};

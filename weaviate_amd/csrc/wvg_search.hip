@@ -1321,7 +1321,8 @@ static StreamLayout stream_layout(const SearchPlan &p1, uint32_t nq, uint32_t k)
 // Workspace of the shared-row query stream (after the status block): partial
 // lists [nq][groups][k], the ready words [nq][groups] (zeroed per call by the
 // prologue launch), then the prologue's seeds [nq] (8 bytes each), the screen's
-// query side -- bf16 images [nq][128] (d = 128 only) and bound constants [nq]
+// query side -- bf16 images [nq][128] (d = 128 only; whole passes of 16, which
+// the shadow-fed scan reads as fragments) and bound constants [nq]
 // (16 bytes each) -- the tools build's screen counter, and the prologue's
 // partial lists [nq][seed_tiles][min(k, 64)] (QSharePro::lists).
 struct QShareLayout {
@@ -1336,7 +1337,7 @@ static QShareLayout qshare_layout(const wvg_corpus *c, const SearchPlan &p1, uin
     l.ready = l.partials + align_up((size_t)nq * l.groups * k * 8, 256);
     l.seeds = l.ready + align_up((size_t)nq * l.groups * 4, 256);
     l.qbf = l.seeds + align_up((size_t)nq * 8, 256);
-    l.qconst = l.qbf + (c->dim == 128 ? align_up((size_t)nq * 128 * 2, 256) : 0);
+    l.qconst = l.qbf + (c->dim == 128 ? (size_t)((nq + 15) / 16) * 16 * 128 * 2 : 0);
     l.count = l.qconst + (c->dim == 128 ? align_up((size_t)nq * 16, 256) : 0);
     l.lists = l.count + 256;
     l.seed_tiles = qshare_seed_tiles(c->dim, p1.te - p1.tb, l.groups);
@@ -1368,6 +1369,14 @@ static wvg_stream_plan stream_plan(const wvg_corpus *c, const SearchPlan &p1, ui
     sp.seeded = *seed_tiles > 0;
     sp.screened = c->ctx->qshare_screen && qshare_screened(c->metric, c->dim, k, *seed_tiles);
     return sp;
+}
+
+// A screened launch may read the corpus's bf16 shadow (scan_f32_qshare_shadow_kernel) in a context that
+// lets batches use it: batch_screen = 0 keeps the stream off the shadow too.  Whether it does is then
+// ensure_shadow's answer at the call.
+static bool stream_shadow_route(const wvg_corpus *c, const wvg_stream_plan &sp)
+{
+    return sp.screened && c->ctx->opt.batch_screen != 0 && tuning().qshare_shadow != 0;
 }
 
 // ---- BQ corpora in the pipelined search ----------------------------------------------------------
@@ -1493,6 +1502,25 @@ int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg
     }
     uint32_t seed_tiles;
     *out = stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k, &seed_tiles);
+    return WVG_OK;
+}
+
+int wvg_search_device_pipelined_shadow(wvg_corpus *c, uint32_t nq, uint32_t k, uint32_t *reads_shadow,
+                                       uint32_t *shadow_bytes_per_row)
+{
+    if (reads_shadow) *reads_shadow = 0;
+    if (shadow_bytes_per_row) *shadow_bytes_per_row = 0;
+    wvg_stream_plan sp;
+    const int rc = wvg_search_device_pipelined_plan(c, nq, k, &sp);
+    if (rc != WVG_OK) return rc;
+    std::shared_lock<std::shared_mutex> lk(c->rw);
+    if (c->kind != WVG_KIND_F32 || !stream_shadow_route(c, sp)) return WVG_OK;
+    {
+        std::lock_guard<std::mutex> g(c->sh_mu);
+        if (c->sh_failed) return WVG_OK;  // a failed allocation: the fp32-screened kernel until the corpus changes
+    }
+    if (reads_shadow) *reads_shadow = 1;
+    if (shadow_bytes_per_row) *shadow_bytes_per_row = 64 * screen_kblocks(c->dim, true) + 4;
     return WVG_OK;
 }
 
@@ -1797,6 +1825,15 @@ static int search_pipelined(wvg_corpus *c, const float *d_queries, uint32_t nq, 
             a.qbf = (uint16_t *)(w + l.qbf);
             a.qconst = (float4 *)(w + l.qconst);
             a.screen_count = (uint64_t *)(w + l.count);
+            // the shadow-fed scan where the corpus's shadow is there (built here on first use, rebuilt over
+            // the rows written since; under the shared corpus lock, as the batch path's); otherwise -- an
+            // allocation failure, a capture without a current shadow -- the fp32-screened kernel
+            if (stream_shadow_route(c, sp) && ensure_shadow(c, s) && !c->sh_i8) {
+                a.screen = 2;
+                a.shadow = c->d_shadow;
+                a.norms = c->d_norms;
+                a.hg = screen_l2_hg(c->dim);
+            }
         }
         const QSharePro pro{(uint64_t *)(w + l.lists), (uint32_t *)(w + WS_SEED_ARRIVALS)};
         WVG_HIP(launch_qshare_seed(a, pro, s, flt));  // zeroes the ready words, writes the seeds

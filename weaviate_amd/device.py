@@ -8,7 +8,7 @@ torch.distributed).
 from __future__ import annotations
 
 import ctypes
-from ctypes import byref, c_int, c_uint64, c_void_p
+from ctypes import byref, c_int, c_uint32, c_uint64, c_void_p
 
 import numpy as np
 
@@ -256,6 +256,15 @@ class Corpus:
         sp = StreamPlan()
         check(self.lib.wvg_search_device_pipelined_plan(self.handle, nq, k, byref(sp)))
         return {name: int(getattr(sp, name)) for name, _ in StreamPlan._fields_}
+
+    def search_device_shadow(self, nq: int, k: int) -> dict:
+        """wvg_search_device_pipelined_shadow: {reads_shadow, shadow_bytes_per_row} -- whether the next
+        search_device_pipelined(nq, k) outside a stream capture reads the corpus's bf16 shadow, and what the
+        first such call allocates per row of capacity (it also builds the shadow: one pass over the rows).
+        Host only."""
+        rs, bpr = c_uint32(), c_uint32()
+        check(self.lib.wvg_search_device_pipelined_shadow(self.handle, nq, k, byref(rs), byref(bpr)))
+        return {"reads_shadow": int(rs.value), "shadow_bytes_per_row": int(bpr.value)}
 
     def batch_plan(self, nq: int, k: int, allow: bool = False) -> dict:
         """wvg_search_batch_plan: the route a batch of nq queries takes on this corpus -- {matrix, screen,

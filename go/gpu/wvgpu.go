@@ -948,7 +948,12 @@ func (x *Corpus) WorkspaceSize(nq, k int) uint64 {
 	return uint64(C.wvg_search_workspace_size(x.h, C.uint32_t(nq), C.uint32_t(k)))
 }
 
-// SearchDevice: nq searches on the device, asynchronous on b.Stream.
+// SearchDevice: nq searches on the device, asynchronous on b.Stream.  Any k: up
+// to 256 the fused top-k; above, the device select route (keys for groups of 4
+// queries, radix select, exact-count compaction, sort), still without a host
+// synchronization or an allocation and capturable in a graph.  Per query the
+// result is Search's for that query alone.  Size the workspace with
+// WorkspaceSize(nq, k) for the k of the call.
 func (x *Corpus) SearchDevice(b DeviceBuffers, nq, k int) error {
 	defer pin(x)()
 	return err(C.wvg_search_device(x.h, (*C.float)(b.Queries), C.uint32_t(nq), C.uint32_t(k), (*C.uint64_t)(b.IDs),

@@ -339,7 +339,35 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * corpus, and for a PQ corpus with a codebook, the size is the largest of
  * wvg_search_device's layout and the pipelined ones (status block, partial
  * lists [nq][row ranges][k], the queries' codes or LUTs); it never got
- * smaller than it was.                                                     */
+ * smaller than it was.
+ * Any k: up to 256 wvg_search_device uses the fused register top-k; above,
+ * the select route on the device (F32 with dim % 4 == 0, every metric and both
+ * distance orders; BQ; PQ with any (m, ks)), with the same guarantees:
+ * asynchronous on `stream`, nothing read from or written to host memory, no
+ * synchronization, no allocation, capturable, the status block untouched, and
+ * on any error nothing launched.  The queries run in groups of G = 4 on the
+ * stream, one group after another through one block of keys: the ordered
+ * 32-bit distance key of every slot for each query of the group (L2 / dot /
+ * cosine rows of d >= 8 in the AVX2 order: one pass over the rows for the
+ * whole group, each 64-row tile loaded once; everywhere else one pass per
+ * query), a radix select of the k-th key per query, a compaction that keeps
+ * the keys below it and, in slot order, as many of the rows equal to it as
+ * the result holds -- exactly min(k, live rows) entries however many rows
+ * tie -- a sort, and the emit; no workgroup waits for another.  Per query the
+ * outputs are wvg_search's for that query alone, bit for bit: ids ascending
+ * by (distance, docID), counts = min(k, live rows), padding ids UINT64_MAX
+ * and dists +inf.  k at or above the corpus's slot count skips the select; a
+ * corpus of more than 2^32 slots answers WVG_ERR_UNSUPPORTED for k > 256 (the
+ * keys hold the slot in 32 bits, as the host path's).  For k > 256
+ * wvg_search_workspace_size returns this route's bytes, which depend on the
+ * corpus geometry, nq and k alone and grow with G x slots, not nq x slots:
+ *   256 (status block) + G x slots x 4 (keys) + G x 16 (select states)
+ *   + G x 4096 x 4 (histograms) + G x ceil(slots / 2048) x 8 (range counts)
+ *   + G x 8 (totals) + 2 x G x k x 8 (compacted and sorted entries)
+ *   + the sort's temporary storage for k entries
+ *   + the queries' codes or LUTs for all nq queries, as for k <= 256,
+ * every piece rounded up to 256 bytes, slots = 64 x the corpus's tiles.  The
+ * pipelined, grouped and multi-GPU entry points keep k <= 256.             */
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k);
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                       uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,

@@ -293,4 +293,15 @@ int bq_rescore_large(wvg_corpus *bq, wvg_corpus *f32, const float *queries, uint
                      const uint64_t *allow_bits, uint64_t allow_words, const SearchPlan &p, uint64_t *out_ids,
                      float *out_dists, uint32_t *out_counts);
 
+// ---- device search for k > MAX_K (wvg_dselect.hip) --------------------------------
+// Queries per group: the group's keys are made in one pass over the rows where the
+// shared-row keys kernel applies, and its select / compaction / emit launches are
+// batched over the group.  The workspace holds DSEL_G key arrays, not nq.
+constexpr int DSEL_G = 4;
+// Bytes behind the status block for a call over nslots slots (depends only on the
+// corpus geometry, nq and k).
+size_t dsel_workspace_bytes(const wvg_corpus *c, uint64_t nslots, uint32_t nq, uint32_t k);
+int dsel_search(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k, const SearchPlan &p, uint64_t *d_ids,
+                float *d_dists, uint32_t *d_counts, char *ws, size_t ws_bytes, hipStream_t s);
+
 }  // namespace wvg

@@ -1549,6 +1549,10 @@ int wvg_search_batch_plan(wvg_corpus *c, uint32_t nq, uint32_t k, int shared_all
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
 {
     if (!c) return 0;
+    if (k > MAX_K) {  // wvg_search_device's select route (the other entry points stop at MAX_K)
+        const SearchPlan ps = plan_search(c, nq, MAX_K, nullptr, 0);
+        return WS_STATUS_BYTES + dsel_workspace_bytes(c, (ps.te - ps.tb) * 64, nq, k);
+    }
     const uint32_t kk = std::max<uint32_t>(k, 1);
     SearchPlan p = plan_search(c, nq, k, nullptr, 0);
     const size_t dev = WS_STATUS_BYTES + align_up(p.workspace_bytes(nq, kk), 256) + device_query_bytes(c, nq);
@@ -1993,17 +1997,21 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
                       uint32_t *d_counts, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     if (!c) return fail(WVG_ERR_INVALID, "null corpus");
-    if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "k above 256 is not supported by the fused top-k");
     if (c->kind == WVG_KIND_F32 && c->dim % 4 != 0)
         return fail(WVG_ERR_UNSUPPORTED, "device search needs dim % 4 == 0");
     if (c->kind == WVG_KIND_PQ && !c->d_centers) return fail(WVG_ERR_INVALID, "PQ corpus has no codebook");
     if (nq == 0 || k == 0) return WVG_OK;
     hipStream_t s = (hipStream_t)stream;
     std::shared_lock<std::shared_mutex> lk(c->rw);
-    SearchPlan p = plan_search(c, nq, k, nullptr, 0);
+    SearchPlan p = plan_search(c, nq, std::min(k, MAX_K), nullptr, 0);
     if (p.empty) {  // empty corpus / slab (e.g. a rank with no rows): empty results
         WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));
         return WVG_OK;
+    }
+    if (k > MAX_K) {  // beyond the fused register top-k: keys, select, compaction and sort in HBM (wvg_dselect.hip)
+        if (!d_workspace || workspace_bytes < WS_STATUS_BYTES) return fail(WVG_ERR_INVALID, "workspace too small");
+        return dsel_search(c, d_queries, nq, k, p, d_ids, d_dists, d_counts, (char *)d_workspace + WS_STATUS_BYTES,
+                           workspace_bytes - WS_STATUS_BYTES, s);
     }
     const size_t part = align_up(p.workspace_bytes(nq, k), 256);
     if (!d_workspace || workspace_bytes < WS_STATUS_BYTES + part + device_query_bytes(c, nq))

@@ -5,7 +5,11 @@ exact-count compaction, sort, emit, all on the caller's stream.
 The reference is Corpus.search(qs, k), the host path (search_large_k: S1-S4 of wvg_select.hip, one
 query at a time), on the same corpus; tests/test_gpu_select.py pins that path to the oracle.  The
 comparison is on ids, distance bits, counts and padding.  For cosine the device call takes the
-normalized queries and the host call the raw ones (it normalizes them itself)."""
+normalized queries and the host call the raw ones (it normalizes them itself).
+
+The corpora here stay below 8,000 rows: every CU-capped grid makes one trip and dsel_scan_kernel gives
+each thread one range.  tests/test_gpu_select_wrap.py holds the large sizes (a wave's second and third
+tile, the compaction's second trip, two and three ranges per scan thread)."""
 import numpy as np
 import pytest
 

@@ -1114,6 +1114,36 @@ func (x *Corpus) SearchDevicePipelinedFiltered(b DeviceBuffers, nq, k int, allow
 		(*C.float)(b.Dists), (*C.uint32_t)(b.Counts), b.Workspace, C.size_t(b.WsBytes), b.Stream))
 }
 
+// DeviceBQRescoreWorkspaceSize: bytes of the workspace SearchDeviceBQRescore
+// needs for nq queries (zero-filled once, like every device workspace).
+func DeviceBQRescoreWorkspaceSize(bq, f32 *Corpus, nq, k, rescoreLimit int) uint64 {
+	defer pin(bq)()
+	defer pin(f32)()
+	return uint64(C.wvg_search_device_bq_rescore_workspace_size(bq.h, f32.h, C.uint32_t(nq), C.uint32_t(k),
+		C.uint32_t(rescoreLimit)))
+}
+
+// SearchDeviceBQRescore: flat.searchByVectorBQ (V/flat/index.go:347-389) on
+// device pointers, asynchronous on b.Stream: the Hamming top-R of bq, R =
+// max(rescoreLimit, k), rescored exactly against the resident rows of f32 in
+// one launch, top-k.  allow.Words == nil: unfiltered; allow lists need R <=
+// 256.  The (distance, docID)-lexicographic result, i.e. SearchBQRescore's in a
+// HeapReplay = 0 context; the heaps' own tie order needs the host call.
+func SearchDeviceBQRescore(bq, f32 *Corpus, b DeviceBuffers, nq, k, rescoreLimit int, allow DeviceAllow) error {
+	defer pin(bq)()
+	defer pin(f32)()
+	if nq < 0 || k < 0 || rescoreLimit < 0 {
+		return errors.New("wvgpu: negative nq, k or rescore limit")
+	}
+	if allow.Words != nil && allow.Stride > 0 && (allow.Bytes/8/allow.Stride < uint64(nq)) {
+		return fmt.Errorf("wvgpu: allow window of %d bytes holds fewer than %d rows of %d words", allow.Bytes, nq,
+			allow.Stride)
+	}
+	return err(C.wvg_search_device_bq_rescore(bq.h, f32.h, (*C.float)(b.Queries), C.uint32_t(nq), C.uint32_t(k),
+		C.uint32_t(rescoreLimit), (*C.uint64_t)(allow.Words), C.uint64_t(allow.Stride), C.uint64_t(allow.FirstID),
+		(*C.uint64_t)(b.IDs), (*C.float)(b.Dists), (*C.uint32_t)(b.Counts), b.Workspace, C.size_t(b.WsBytes), b.Stream))
+}
+
 // CheckDevice surfaces a device-side failure of earlier device searches.
 func (c *Ctx) CheckDevice(workspace, stream unsafe.Pointer) error {
 	defer pin(c)()

@@ -461,6 +461,45 @@ int wvg_search_device_pipelined_filtered(wvg_corpus *c, const float *d_queries, 
                                          uint64_t allow_first_id, uint64_t *d_ids, float *d_dists,
                                          uint32_t *d_counts, void *d_workspace, size_t workspace_bytes,
                                          void *stream);
+/* flat.searchByVectorBQ (V/flat/index.go:347-389) for a caller whose queries
+ * and results stay in HBM: both halves on `stream`, nothing on the host.
+ * R = max(rescore_limit, k) (index.go:297-305).  Stage 1 takes the (Hamming
+ * distance, docID)-lexicographic top-R of `bq` per query into the workspace:
+ * R <= 256 by wvg_search_device_pipelined_filtered's routes (d_allow,
+ * allow_stride, allow_first_id as there; d_allow NULL: unfiltered), R > 256 by
+ * wvg_search_device's select route, which has no filter -- an allow list with
+ * R > 256 answers WVG_ERR_UNSUPPORTED.  Stage 2 is ONE launch for all nq
+ * queries: a workgroup per query maps every candidate docID to its slot of
+ * `f32`, skips the candidates that are not live rows there (deleted from the
+ * float corpus, or outside its capacity), reads each row once -- eight lanes per row, every lane's 16-byte
+ * chunks in flight together -- computes the exact distance in the context's
+ * distance order (wvg_set_distance_order) with the metric's Wrap, keeps a
+ * register top-k per wave and writes the merged [k] ids, distances, count and
+ * padding.  No per-candidate distance goes through memory.
+ * Result per query, bit for bit: the (exact distance, docID)-lexicographic
+ * top-k of the rescored candidates, ascending, counts and padding as
+ * wvg_search -- what wvg_search_bq_rescore returns in a context opened with
+ * heap_replay = 0.  The order Weaviate's heaps keep among ties at the R-th
+ * Hamming distance and among equal exact distances needs the host replay and
+ * stays with wvg_search_bq_rescore in heap_replay = 1 contexts.
+ * As the other device calls: asynchronous on `stream`, no host memory read or
+ * written, no synchronization, no allocation, capturable, the status block
+ * untouched, and on any error nothing launched.  d_queries: float [nq][dim],
+ * normalized by the caller for cosine.  `bq` (BQ) and `f32` (F32) must share
+ * context, dim, metric (l2-squared, dot or cosine) and id_base:
+ * WVG_ERR_INVALID otherwise.  k > 256 or dim > 8192: WVG_ERR_UNSUPPORTED.
+ * nq == 0 or k == 0: nothing to do; an empty corpus (either one): empty
+ * results.  d_counts may be NULL.  The workspace (zero-filled once, like
+ * every device workspace; _workspace_size bytes) begins with stage 1's own --
+ * wvg_search_workspace_size(bq, nq, R) -- followed by the candidates' ids,
+ * Hamming distances and counts.  One workgroup serves a query whatever R is,
+ * so stage 2 grows linearly with R (it is sized for R of a few hundred).     */
+size_t wvg_search_device_bq_rescore_workspace_size(wvg_corpus *bq, wvg_corpus *f32, uint32_t nq, uint32_t k,
+                                                   uint32_t rescore_limit);
+int wvg_search_device_bq_rescore(wvg_corpus *bq, wvg_corpus *f32, const float *d_queries, uint32_t nq, uint32_t k,
+                                 uint32_t rescore_limit, const uint64_t *d_allow, uint64_t allow_stride,
+                                 uint64_t allow_first_id, uint64_t *d_ids, float *d_dists, uint32_t *d_counts,
+                                 void *d_workspace, size_t workspace_bytes, void *stream);
 /* What wvg_search_device_pipelined(c, ..., nq, k, ...) will do, for a caller
  * that sizes its batches to fill whole passes.  Host only: no device call,
  * nothing launched; computed by the functions the search itself routes with.

@@ -430,6 +430,22 @@ def search_bq_rescore(bq: Corpus, f32: Corpus, queries, k: int, rescore_limit: i
     return ids, dists, counts
 
 
+def search_device_bq_rescore_workspace_size(bq: Corpus, f32: Corpus, nq: int, k: int, rescore_limit: int) -> int:
+    """wvg_search_device_bq_rescore_workspace_size: bytes of the (once zero-filled) device workspace."""
+    return int(bq.lib.wvg_search_device_bq_rescore_workspace_size(bq.handle, f32.handle, nq, k, rescore_limit))
+
+
+def search_device_bq_rescore(bq: Corpus, f32: Corpus, d_queries: int, nq: int, k: int, rescore_limit: int, d_ids: int,
+                             d_dists: int, d_counts: int, d_workspace: int, workspace_bytes: int, stream: int = 0,
+                             d_allow: int = 0, allow_stride: int = 0, allow_first_id: int = 0) -> None:
+    """wvg_search_device_bq_rescore on device pointers, asynchronous on `stream`: the Hamming top-R
+    (R = max(rescore_limit, k)) of `bq`, rescored exactly against the rows of `f32`, top-k; d_allow as
+    Corpus.search_device_pipelined (R <= 256 only)."""
+    check(bq.lib.wvg_search_device_bq_rescore(bq.handle, f32.handle, d_queries, nq, k, rescore_limit, d_allow or None,
+                                              allow_stride, allow_first_id, d_ids, d_dists, d_counts or None,
+                                              d_workspace, workspace_bytes, stream or None))
+
+
 class Multi:
     """wvg_multi_open / wvg_multi_close: one context per device in this process
     and, for distinct devices, an RCCL communicator per device."""

@@ -96,6 +96,12 @@ typedef struct wvg_options {
                                   screen (shadow: 2 * dim + 4 bytes per row, at the first screened
                                   batch); 0: the co-scheduled per-query scans, as batches of fewer than
                                   mfma_min_queries.
+                                  3 (opt-in): as 2, and l2-squared batches at d = 512 / 768 / 1024 screen
+                                  with int8 MFMA too (K3i-L2; shadow: dim + 8 bytes per row, half the
+                                  bf16 one; other d, an empty or all-zero corpus: the bf16 screen).
+                                  Measured with 1024-query batches, k = 10: 12.95 against 23.2 ms at
+                                  10M x 768, 4.52 against 5.84 ms at 1M x 1024, 5.40 against 5.67 ms at
+                                  1M x 768, but slower at 1M x 512 (3.87 against 3.65 ms).
                                   The first screened search of a corpus allocates its shadow: int8 = dim
                                   + 8 bytes per row of capacity (7.7 GB at 10M x 768; its first build
                                   also takes one pass over the rows for the corpus scale and one host
@@ -548,8 +554,10 @@ int wvg_search_device_pipelined_shadow(wvg_corpus *c, uint32_t nq, uint32_t k, u
  * routes with.  Answers for every kind and metric: F32 dot / cosine /
  * l2-squared batches of at least mfma_min_queries report matrix = 1 and their
  * screen (l2-squared: the bf16 screen, 1, where it applies -- d % 32 == 0,
- * k <= 16, the AVX2 order, batch_screen != 0 -- and no matrix path at all
- * elsewhere); BQ / PQ corpora, other metrics, smaller batches, k > 256, an
+ * k <= 16, the AVX2 order, batch_screen != 0 -- or under batch_screen = 3 at
+ * d = 512 / 768 / 1024 the int8 screen, 2, with dim + 8 shadow bytes per row
+ * (1 again once the corpus's shadow fell back to bf16), and no matrix path at
+ * all elsewhere); BQ / PQ corpora, other metrics, smaller batches, k > 256, an
  * empty corpus, nq == 0 or k == 0: all zero.  shared_allow_list != 0: the
  * batch carries one allow list for all its queries; the route is the same.
  * Per-query allow windows never take the matrix path.                      */

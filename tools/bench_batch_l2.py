@@ -71,10 +71,12 @@ def main():
             check(lib.wvg_search_device(c.handle, tq.data_ptr(), nq, k, oi.data_ptr(), od.data_ptr(), oc.data_ptr(),
                                         ws.data_ptr(), wsb, st))
 
+        free0 = torch.cuda.mem_get_info(dev)[0]
         t0 = time.time()
         run()  # a screened route builds the shadow here
         torch.cuda.synchronize()
         first_s = time.time() - t0
+        shadow_bytes = free0 - torch.cuda.mem_get_info(dev)[0]  # what the first call allocated and kept
         run()
         torch.cuda.synchronize()
         check(lib.wvg_profile_start(ctx.handle))
@@ -86,7 +88,16 @@ def main():
         ms, nl = ctypes.c_double(), ctypes.c_uint64()
         check(lib.wvg_profile_stop(ctx.handle, ctypes.byref(ms), ctypes.byref(nl)))
         kern_ms = ms.value / max(1, a.reps)
-        out = {"label": a.label, "config": f"{n} x {d} {a.metric}, {nq} queries, k={k}, batch_screen={a.batch_screen}",
+        each = []  # every batch on its own (a synchronize per batch): the spread
+        for _ in range(max(a.reps, 10)):
+            t0 = time.time()
+            run()
+            torch.cuda.synchronize()
+            each.append((time.time() - t0) * 1e3)
+        p10, med, p90 = (round(float(x), 3) for x in np.percentile(each, [10, 50, 90]))
+        out = {"batch_ms_median": med, "batch_ms_p10_p90": [p10, p90], "shadow_bytes_measured": int(shadow_bytes),
+               "shadow_bytes_per_row_measured": round(shadow_bytes / n, 2)}
+        out |= {"label": a.label, "config": f"{n} x {d} {a.metric}, {nq} queries, k={k}, batch_screen={a.batch_screen}",
                "plan": plan, "lib": os.path.relpath(LIB_PATH, os.path.dirname(HERE)), "batch_ms": round(wall * 1e3, 3), "qps": round(nq / wall, 1),
                "scoring_ms_per_batch": round(kern_ms, 3), "profiled_launches": int(nl.value),
                "first_call_s": round(first_s, 3),

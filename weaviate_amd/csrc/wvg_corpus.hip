@@ -115,9 +115,8 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s)
         // scale S = the largest finite |x| / 127 of the rows written so far (one pass and
         // one host wait, at the shadow's first build); no rows / all zeros / an extreme
         // scale keep the bf16 shadow
-        // (an l2-squared corpus: always bf16, K3c-L2 is its one screen)
-        bool i8 = c->ctx->opt.batch_screen == 2 && c->metric != WVG_METRIC_L2 && screen_i8_supported(c->dim) &&
-                  c->high_water > 0;
+        // (an l2-squared corpus: bf16 and K3c-L2 unless the context asks for K3i-L2, batch_screen = 3)
+        bool i8 = shadow_wants_i8(c) && c->high_water > 0;
         float sc[2] = {1.f, 1.f};
         if (i8) {
             uint32_t amax_bits = 0;

@@ -161,6 +161,13 @@ void shadow_free(wvg_corpus *c);
 // The bf16 / int8 shadow of an F32 dot / cosine / l2-squared corpus, ready for a screen on stream
 // s (built or refreshed there, or waited for).  False: run the exact path.
 bool ensure_shadow(wvg_corpus *c, hipStream_t s);
+// Whether a first build of c's shadow tries the int8 one (K3i; an l2-squared corpus: K3i-L2, only
+// under batch_screen = 3).  No rows, all zeros or an extreme scale still fall back to bf16.
+inline bool shadow_wants_i8(const wvg_corpus *c)
+{
+    const int bs = c->ctx->opt.batch_screen;
+    return (c->metric == WVG_METRIC_L2 ? bs == 3 : bs == 2 || bs == 3) && wvg::screen_i8_supported(c->dim);
+}
 
 // ---- search planning (wvg_search.hip) ------------------------------------------
 // Workspace of a K3c / K3d screen (wvg_screen.hip): range lists, candidates,

@@ -629,7 +629,7 @@ struct ScreenLaunch {
     bool i8 = false;
     const float *errs = nullptr;
     float *kb = nullptr, *css = nullptr, *qinv = nullptr;  // [nq_pad]
-    // K3c-L2 (an l2-squared corpus; bf16 shadow): per-query Cq [nq_pad]; cosine = 0
+    // K3c-L2 / K3i-L2 (an l2-squared corpus; bf16 shadow, or int8 with i8 set): per-query Cq [nq_pad]; cosine = 0
     bool l2 = false;
     float *cq = nullptr;
     uint32_t *gbound;      // [nq]

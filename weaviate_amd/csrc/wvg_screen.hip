@@ -12,6 +12,9 @@
 //   K3c-L2  screen_l2_kernel: K3c's body with the l2-squared bound and
 //        threshold space (below, "K3c-L2"); the one screen of an l2-squared
 //        corpus, any d % 32 == 0, bit-identical to K1's l2_256 order.
+//   K3i-L2  screen_i8_l2_kernel<KBN> (d = 512 / 768) and screen_ar_l2_kernel
+//        <16> (d = 1024): K3i with K3c-L2's bound (below, "K3i-L2"); an
+//        l2-squared corpus in a batch_screen = 3 context.
 // A non-zero DIAG instantiates a timing / counting diagnostic of K3d or K3i
 // (tools build only).  Results are bit-identical to the exact path (K3b / K1,
 // the reference's AVX2-order dot_256):
@@ -1785,9 +1788,13 @@ static_assert(SJ_LDS <= 160 * 1024, "K3i 2x2's LDS");
 // DIAG (tools build only; 0 in the product): 16 = counters (wave row blocks, active groups,
 // inserts, groups with a passing element), 4 = fast check but no slow path, 10 = no epilogue
 // (the accumulators consumed by one sum) -- timing only, results are not search results.
-template <int KBN, int DIAG = 0>
-__global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs a)
+// L2 (K3i-L2, below: the int8 shadow of an l2-squared corpus): the epilogue and threshold space of
+// "K3i-L2"; cqp = the queries' Cq, hg = the rows' (1 - g) / 2.  L2 = false: cqp / hg unused (the dot /
+// cosine instantiations keep their register counts with the flag; K3d's do not, see screen_ar_l2_kernel).
+template <int KBN, int DIAG, bool L2>
+__device__ __forceinline__ void screen_i8_body(const ScreenArgs &a, const float *cqp, float hg)
 {
+    static_assert(!L2 || DIAG == 0, "no diagnostic has an l2-squared form");
     static_assert(KBN <= 12, "64 resident queries x KBN K blocks must fit the registers");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint64_t *lists = reinterpret_cast<uint64_t *>(smem + SJ_RING);  // [4 waves][64][M]
@@ -1798,6 +1805,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
     float *cem = ck2 + SD_BQ;                                             // Emax
     float *ckb = cem + SD_BQ;                                             // B
     float *ccs = ckb + SD_BQ;                                             // score scale
+    float *ccq = ccs + SD_BQ;                                             // (L2) Cq
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     uint32_t n_blk = 0, n_grp = 0, n_pass = 0, n_ins = 0;  // (DIAG 16, tools)
@@ -1816,11 +1824,19 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
     sc_copy_consts<true>(a, q0, SD_WAVES * 64, ck1, ck2, cem, ckb, ccs);
     sc_init_thresholds<64, 2, SD_WAVES>(a, q0, tid, cosine, tau, sig);  // 2 query halves x 2 row halves
     for (int i = tid; i < SD_WAVES * 64 * M; i += SD_WAVES * 64) lists[i] = WVG_KEY_NONE;
+    if constexpr (L2) {
+        for (int i = tid; i < SD_BQ; i += SD_WAVES * 64) ccq[i] = cqp[q0 + (uint32_t)i];
+        __syncthreads();  // tau is in place: its u-space form with the query's Cq (slot (w, ql) = query 64 (w & 1) + ql)
+        for (int i = tid; i < SD_WAVES * 64; i += SD_WAVES * 64) {
+            const int qi = ((i >> 6) & 1) * 64 + (i & 63);
+            sig[i] = q0 + (uint32_t)qi >= a.nq ? __builtin_inff() : sc_sigma_l2(tau[i], ccq[qi]);
+        }
+    }
     __syncthreads();
     SurvivorLists S;
     S.laddr = (uint32_t)(uintptr_t)(lists + (size_t)w * 64 * M);
     // LDS byte addresses: tau[w][0] (sig at + 1024) and ck1[64 wq] (ck2, cem, ckb, ccs at
-    // + 512, + 1024, + 1536, + 2048)
+    // + 512, + 1024, + 1536, + 2048; L2: ccq at + 2560)
     const uint32_t tbase = (uint32_t)(uintptr_t)(tau + w * 64);
     const uint32_t cbase = (uint32_t)(uintptr_t)(ck1 + 64 * wq);
     if (blk0 < blk1) {
@@ -2009,6 +2025,13 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
                 nmax = __builtin_fmaxf(nmax, nrm[j]), nsum += nrm[j];
                 emx = __builtin_fmaxf(emx, err[j]), esum += err[j];
             }
+            float hmin = 0.f;  // (L2) the h of the lane's smallest norm: the most favourable of its 8 rows
+            if constexpr (L2) {
+                float nmin = nrm[0];
+#pragma unroll
+                for (int j = 1; j < 8; j++) nmin = __builtin_fminf(nmin, nrm[j]);
+                hmin = (nmin * nmin) * hg;  // (finite where the check decides: nmax <= 2^60, no NaN)
+            }
             const bool force = lane_force || !(nmax <= 0x1p60f) || nsum != nsum || !(emx <= 0x1p60f) || esum != esum;
             if constexpr (DIAG == 16) n_blk++;
             // fast check per (query group g, query r of the lane's four): the largest exact
@@ -2053,8 +2076,9 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
                     const float svr[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
-                        const float t = ((float)mi[h][r] * csr[r] +
-                                         __builtin_fmaf(emx, k1r[r], __builtin_fmaf(nmax, kbr[r], k2r[r]))) -
+                        const float t = sc_u<L2>((float)mi[h][r] * csr[r],
+                                                 __builtin_fmaf(emx, k1r[r], __builtin_fmaf(nmax, kbr[r], k2r[r])),
+                                                 hmin) -
                                         svr[r];
                         if (__ballot(force || t >= 0.f)) wact |= 1u << (4 * g + r);
                     }
@@ -2116,12 +2140,21 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
                                  : "=v"(ws), "=v"(k1), "=v"(k2), "=v"(kbq), "=v"(csq)
                                  : "v"(ta), "v"(ca)
                                  : "memory");
+                    float cqq = 0.f;  // (L2) Cq
+                    if constexpr (L2)
+                        asm volatile("ds_read_b32 %0, %1 offset:2560\n\t"
+                                     "s_waitcnt lgkmcnt(0)"
+                                     : "=v"(cqq)
+                                     : "v"(ca)
+                                     : "memory");
                     float uu[8];
                     uint64_t any = 0;
 #pragma unroll
                     for (int nr = 0; nr < 8; nr++) {
                         const uint64_t m64 = ((vm[nr >> 2] >> (16 * (nr & 3))) & 0xFFFFull) * 0x0001000100010001ull;
-                        uu[nr] = uv[nr] * csq + __builtin_fmaf(err[nr], k1, __builtin_fmaf(nrm[nr], kbq, k2));
+                        // (L2: h is NaN beyond the norm limit, so the row is a candidate)
+                        uu[nr] = sc_u<L2>(uv[nr] * csq, __builtin_fmaf(err[nr], k1, __builtin_fmaf(nrm[nr], kbq, k2)),
+                                          L2 ? (nrm[nr] <= 0x1p60f ? (nrm[nr] * nrm[nr]) * hg : __builtin_nanf("")) : 0.f);
                         any |= __ballot(!(uu[nr] < ws)) & m64;
                     }
                     if (!any) continue;
@@ -2146,8 +2179,9 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
                             const int j = __builtin_ctzll(pass);
                             pass &= pass - 1;
                             const int gq = j >> 4;
-                            const float lower =
-                                sc_lower(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j)), cosine);
+                            const float uj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j));
+                            const float cqg = L2 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cqq), j)) : 0.f;
+                            const float lower = L2 ? sc_lower_l2(uj, cqg) : sc_lower(uj, cosine);
                             float wtg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wt), j));
                             if (!(lower <= wtg)) continue;
                             const uint64_t key = ((uint64_t)wvg_ord_f32(lower) << 32) |
@@ -2163,7 +2197,7 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
                             const float emg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(em), j));
                             if (nk != WVG_KEY_NONE) wtg = fminf(wtg, sc_tau_k(key_lower(nk), emg, cosine));
                             if (nm != WVG_KEY_NONE) wtg = fminf(wtg, key_lower(nm));
-                            const float wsg = sc_sigma(wtg, cosine);
+                            const float wsg = L2 ? sc_sigma_l2(wtg, cqg) : sc_sigma(wtg, cosine);
                             wt = inrow ? wtg : wt;
                             ws = inrow ? wsg : ws;
                             pass &= ~(0xFFFFull << (16 * gq)) | __ballot(!(u < ws));
@@ -2225,6 +2259,712 @@ __global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs 
             atomicMin(a.gbound + q, wvg_ord_f32(t));
         }
     }
+}
+
+template <int KBN, int DIAG = 0>
+__global__ __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_kernel(ScreenArgs a)
+{
+    screen_i8_body<KBN, DIAG, false>(a, nullptr, 0.f);
+}
+
+// ---------------------------------------------------------------------------
+// K3i-L2: the int8 screen for l2-squared corpora (option batch_screen = 3) --
+// K3i's shadow, staging ring, int8 MFMA tile, lists, partials and tau
+// publication (the 2 x 2 kernel for d = 512 / 768, K3d's 1 x 4 layout for d =
+// 1024); the epilogue and the threshold space are K3c-L2's.
+//
+// The bound.  r, D, Nq, Nx, c_a, alpha, g, hg, beta as in "K3c-L2"; s = fl(fl(
+// acc) fl(S Sq)) the scaled int8 MFMA dot, Ex, Nqt, Eq, A, B, K2 as in "The
+// int8 screen".
+//   (a) the chain: D (1 - c_a) - 2^-130 <= r <= D (1 + c_a) + 2^-130 (K3c-L2).
+//   (b) the dot: |q.x - s| <= T = Nqt Ex (1 + 2^-22.9) + Nx (Eq + 2^-22.9 Nqt)
+//       (Cauchy-Schwarz and s's two roundings; the real dot has no AVX2-chain
+//       term).  E1 = fma(Ex, A, fma(Nx, B, K2)) in fp32 is at least (1 -
+//       2^-23) times its real value (two fma roundings), and A, B carry (1 +
+//       2^-19) and the 4 d 2^-24 Nq term, so
+//         E1 - T >= 2^-20 (Nqt Ex + Nx Eq + Nx Nqt) + 2^-14 Nq Nx (d >= 512):
+//       E1 bounds |q.x - s| on both sides with that much to spare.
+//   (c) the combine, K3c-L2's: h = fl(fl(Nx Nx) hg), w = fl(s - h), u = fl(w +
+//       E1), lower = fl(Cq - 2 u).  Its three roundings move lower by at most
+//       2^-24 (6 |s| + 6 h + 4 E1 + |Cq|).  The part relative to h <= Nx^2 / 2
+//       and |Cq| <= Nq^2 is <= 3 2^-24 (Nq^2 + Nx^2) < 2^-21 (Nq^2 + Nx^2),
+//       which alpha holds as in K3c-L2.  The part relative to |s| <= Nqt (Nx +
+//       Ex) (1 + 2^-22) and E1 -- here E1 may be as large as Nq Nx (a row
+//       above the corpus scale clamps: Ex ~ |x|), so it cannot go into alpha --
+//       is <= 2^-24 (6 Nqt Nx + 10 E1) <= 2 (E1 - T): it is paid from (b)'s
+//       spare, on both sides.  Denormal results (h, s, the fmas) move lower
+//       by < 2^-120, inside Cq's 2^-100.
+// So with 2 h <= |x|^2 - alpha Nx^2 and Cq <= |q|^2 - alpha Nq^2 - 2^-100:
+//   lower <= D - 2 c_a (Nq^2 + Nx^2) - 2^-130 <= r   and
+//   r - lower <= 4 E1 + 2 beta (Nq^2 + Nx^2) + 2^-98 = 2 E_tot,
+//   E_tot = 2 E1 + beta (Nq^2 + Nx^2) + 2^-99,
+// monotone in Ex and in Nx: Emax_q = E_tot at the corpus maxima of both (mx[1],
+// mx[0]; rounded up) bounds it for every row, tau = (k-th smallest lower) +
+// 2 Emax_q holds as in K3c, and lower is clamped at 0 (r >= 0).
+// The fast check runs before the per-row terms, per lane over its 8 (2 x 2) or
+// 16 (1 x 4) rows of a query: mi = the largest exact int32 score, emx / nmax
+// the largest Ex / Nx, and hmin = fl(fl(nmin nmin) hg) the h of the smallest
+// Nx -- the most favourable h of the group.  Every step of u is monotone (fl
+// is; css, A, B, K2 >= 0): s <= fl(mi css), h >= hmin, E1 <= fma(emx, A,
+// fma(nmax, B, K2)), so u <= umax = fl(fl(fl(mi css) - hmin) + E1max) for each
+// of the rows, and umax < sigma_q proves u < sigma_q <= (Cq - tau) / 2
+// (sc_sigma_l2 rounds down), i.e. lower > tau: a superset test in l2's u-space.
+// Non-finite and huge values: a query that is not finite, whose scale is
+// outside the normal range or whose norm bound is above 2^56 gets A = +inf
+// and Cq = -inf; a row with Nx or Ex above 2^60 (inf: a NaN / inf row) gets h
+// = NaN.  Both force the per-element path (lane_force / force), where u is
+// NaN or +inf and the lower bound -inf: a candidate, rescored exactly, never a
+// skip.  Inside the limits every value of the fast check is finite (|fl(mi
+// css)| < 2^124, hmin < 2^120, E1max < 2^112).
+struct ScreenL2I8Args {
+    ScreenL2Args l;  // s: K3i's arguments (cosine = 0; emax the l2 Emax_q); cq, hg: K3c-L2's
+};
+constexpr int SJ_LDS_L2 = SJ_LDS + SD_BQ * 4;  // + the workgroup's Cq
+constexpr int si_lds_l2(int nb) { return si_lds(nb) + SD_BQ * 4; }
+static_assert(SJ_LDS_L2 <= 160 * 1024 && si_lds_l2(8) <= 160 * 1024, "K3i-L2's LDS");
+
+// The K3i-L2 kernels are compiled without packed fp32 instructions (v_pk_add / mul / fma_f32): the bound's
+// fp32 steps are scalar operations, each rounded as the comment block above counts them.
+#ifdef __HIP_DEVICE_COMPILE__
+#define WVG_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define WVG_NO_PK_F32
+#endif
+
+template <int KBN>
+__global__ WVG_NO_PK_F32 __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_l2_kernel(ScreenL2I8Args a)
+{
+    screen_i8_body<KBN, 0, true>(a.l.s, a.l.cq, a.l.hg);
+}
+
+// K3i-L2 on K3d's 1 x 4 layout (d = 1024): screen_ar_kernel<KBN, 0, true>'s body with the l2-squared
+// epilogue and threshold space.  A body of its own: as a flag of screen_ar_kernel's it moved the dot /
+// cosine instantiations' register counts.  DIAG / I8 / L2 are fixed here so the text stays K3d's.
+template <int KBN>
+__device__ __forceinline__ void screen_ar_l2_body(const ScreenArgs &a, const float *cqp, float hg)
+{
+    constexpr int DIAG = 0;
+    constexpr bool I8 = true, L2 = true;
+    constexpr int NB = I8 ? si_nbuf(KBN) : SD_NBUF;  // stage buffers
+    constexpr int NSLOT = I8 ? SI_NSLOT : SD_NSLOT;
+    constexpr int RING = NB * SD_STAGE + 2 * NSLOT;
+    static_assert(KBN % NB == 0, "the stage buffer of a K block must be a compile-time constant");
+    static_assert(DIAG == 0 || DIAG == 10 || (!I8 && (DIAG == 4 || DIAG == 16)),
+                  "diagnostics: 4, 10, 16 (K3i: only the stage-loop one)");
+    using frag_t = std::conditional_t<I8, i32x4, bf16x8>;
+    using acc_t = std::conditional_t<I8, i32x4, floatx4>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem + RING);  // [4][32][M]
+    float *tau = reinterpret_cast<float *>(smem + RING + SD_LISTS);
+    float *sig = tau + SD_WAVES * 32;
+    float *ck1 = sig + SD_WAVES * 32;
+    float *ck2 = ck1 + SD_BQ;
+    float *cem = ck2 + SD_BQ;
+    float *ckb = cem + SD_BQ;  // (I8) B
+    float *ccs = ckb + SD_BQ;  // (I8) score scale
+    float *ccq = ccs + SD_BQ;  // (L2) Cq
+    uint32_t n_blk = 0, n_slow = 0, n_call = 0, n_grp = 0;  // (DIAG 16)
+    (void)n_blk, (void)n_slow, (void)n_call, (void)n_grp;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int K = (int)a.k, M = SCREEN_M;
+    const int cosine = a.cosine;
+    uint32_t qb, rr;
+    sc_block_map(a, qb, rr);
+    const uint64_t ntiles = a.tile_end - a.tile_begin;
+    const uint64_t nblk = (ntiles + 3) / 4;
+    uint64_t blk0, blk1;
+    sc_range(a, nblk, rr, blk0, blk1);
+    const uint32_t q0 = qb * SD_BQ;
+
+    sc_copy_consts<I8>(a, q0, SD_WAVES * 64, ck1, ck2, cem, ckb, ccs);
+    sc_init_thresholds<32, 4, SD_WAVES>(a, q0, tid, cosine, tau, sig);  // 4 query quarters, every row
+    for (int i = tid; i < SD_WAVES * 32 * M; i += SD_WAVES * 64) lists[i] = WVG_KEY_NONE;
+    if constexpr (L2) {
+        for (int i = tid; i < SD_BQ; i += SD_WAVES * 64) ccq[i] = cqp[q0 + (uint32_t)i];
+        __syncthreads();  // tau is in place: its u-space form with the query's Cq (slot (w, ql) = query 32 w + ql)
+        for (int i = tid; i < SD_WAVES * 32; i += SD_WAVES * 64)
+            sig[i] = q0 + (uint32_t)i >= a.nq ? __builtin_inff() : sc_sigma_l2(tau[i], ccq[i]);
+    }
+    __syncthreads();
+    SurvivorLists S;
+    S.laddr = (uint32_t)(uintptr_t)(lists + (size_t)w * 32 * M);
+    // the wave's per-query thresholds WT (tau), their u-space form WS (sig) and Emax
+    // (cem): LDS byte address of tau[w][0]; sig, ck1, ck2, cem at + 512, + 1024, + 1536,
+    // + 2048 (I8: ckb, ccs at + 2560, + 3072; L2: ccq at + 3584)
+    const uint32_t tbase = (uint32_t)(uintptr_t)(tau + w * 32);
+    if (blk0 < blk1) {
+        // the wave's 32 queries, every K block, resident for the whole range
+        frag_t areg[KBN][2];
+        // The first SD_AKB K blocks' fragments live in AGPRs (an MFMA A operand may be
+        // an AGPR), the rest in VGPRs: 128 accumulator + 64 B-fragment + 48 such AGPRs,
+        // which leaves the epilogue ~100 VGPRs -- with all 192 in VGPRs the compiler
+        // spilled query fragments around the epilogue, and a scratch reload before the
+        // loop costs a vmcnt(0) (a drain of the stage ring) at every row block.
+        constexpr int SD_AKB = 6;
+        const uint4 *qsrc = a.qfrag + (size_t)(qb * 8 + 2 * w) * KBN * 64 + lane;
+#pragma unroll
+        for (int ks = 0; ks < KBN; ks++)
+#pragma unroll
+            for (int mq = 0; mq < 2; mq++) {
+                const uint4 *src = qsrc + ((size_t)mq * KBN + ks) * 64;
+                if (ks < SD_AKB)
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(areg[ks][mq]) : "v"(src) : "memory");
+                else
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(areg[ks][mq]) : "v"(src) : "memory");
+            }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int ks = 0; ks < KBN; ks++)
+#pragma unroll
+            for (int mq = 0; mq < 2; mq++) {
+                if (ks < SD_AKB)
+                    asm volatile("" : "+a"(areg[ks][mq]));
+                else
+                    asm volatile("" : "+v"(areg[ks][mq]));
+            }
+
+        // loads of one stage: wave w moves row fragments 4w .. 4w+3 (tile w,
+        // row groups 0..3); with unit 0 also the norms of tile w, and wave 0
+        // the block's tile words (sd_unit_loads).  Round 3 reloaded the norms
+        // and words with every unit: 25 % more LDS-DMA issues per unit.
+        const uint4 *lsrc = a.shadow + ((size_t)(a.tile_begin + blk0 * 4 + w) * KBN * 4) * 64 + lane;
+        const float *lnorm = a.norms + (a.tile_begin + blk0 * 4 + w) * 64 + lane;
+        const float *lerr = I8 ? a.errs + (a.tile_begin + blk0 * 4 + w) * 64 + lane : nullptr;
+        uint64_t lblk = blk0;
+        auto load_stage = [&](int ks) {
+            unsigned char *dst = smem + (ks % NB) * SD_STAGE;
+#pragma unroll
+            for (int rg = 0; rg < 4; rg++)
+                __builtin_amdgcn_global_load_lds(lsrc + ((size_t)ks * 4 + rg) * 64,
+                                                 reinterpret_cast<uint4 *>(dst + (4 * w + rg) * 1024), 16, 0, 0);
+            unsigned char *nslot = smem + NB * SD_STAGE + (lblk & 1) * NSLOT;
+            // the block's norms / tile words with its unit 0 (sd_unit_loads: the waits count them)
+            const bool with_norms = ks == 0;
+            if (with_norms)
+                __builtin_amdgcn_global_load_lds(lnorm, reinterpret_cast<float *>(nslot + w * 256), 4, 0, 0);
+            if (I8 && with_norms)
+                __builtin_amdgcn_global_load_lds(lerr, reinterpret_cast<float *>(nslot + 1280 + w * 256), 4, 0, 0);
+            if (with_norms && w == 0) {
+                __builtin_amdgcn_global_load_lds(sc_tile_word_src(a, lblk, lane),
+                                                 reinterpret_cast<uint32_t *>(nslot + 1024), 4, 0, 0);
+            }
+            if (ks == KBN - 1 && lblk + 1 < blk1) {  // the load cursor moves on; past the end it stays
+                ++lblk;
+                lsrc += (size_t)4 * KBN * 4 * 64;
+                lnorm += 256;
+                if constexpr (I8) lerr += 256;
+            }
+        };
+        // six stages in flight at every wait: unit ks + 1 (waited for at K block ks) + the 5
+        // younger units ks + 2 .. ks + 6, whose loads the wait leaves outstanding
+        // (K3i with NB = 6: four stages in flight, three left outstanding)
+        auto wait_next = [&](auto KS) {
+            constexpr int ks = decltype(KS)::value;
+            constexpr int n0 = sd_younger<KBN, I8>(ks + 1, NB - 3, true);
+            constexpr int n1 = sd_younger<KBN, I8>(ks + 1, NB - 3, false);
+            if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n0) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n1) : "memory");
+        };
+        auto raw_barrier = [&]() {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        };
+        // Half a stage's row fragments straight into AGPRs (the MFMA B operand may
+        // be an AGPR): the 512 registers hold the resident queries (192 VGPRs), the
+        // accumulators (128 AGPRs) and both halves (64 AGPRs), which leaves the
+        // VGPRs the epilogue needs.  The reads are asynchronous to the compiler:
+        // every consumer first passes a wait that names the registers (wait_b0,
+        // and the barrier's lgkmcnt(0) + the "+a" fence for the second half).
+        // One lane base address for every read: the stage / half offset is added
+        // inside the asm from an SGPR (16 precomputed addresses cost 16 VGPRs).
+        const uint32_t rbase = (uint32_t)(uintptr_t)smem + 16u * lane;
+        auto read_half = [&](int ks, int h, frag_t (&br)[8]) {
+            const uint32_t soff = (uint32_t)((ks % NB) * SD_STAGE + h * 8 * 1024);
+            uint32_t tmp;
+            asm volatile("v_add_u32 %8, %9, %10\n\t"
+                         "ds_read_b128 %0, %8\n\t"
+                         "ds_read_b128 %1, %8 offset:1024\n\t"
+                         "ds_read_b128 %2, %8 offset:2048\n\t"
+                         "ds_read_b128 %3, %8 offset:3072\n\t"
+                         "ds_read_b128 %4, %8 offset:4096\n\t"
+                         "ds_read_b128 %5, %8 offset:5120\n\t"
+                         "ds_read_b128 %6, %8 offset:6144\n\t"
+                         "ds_read_b128 %7, %8 offset:7168"
+                         : "=a"(br[0]), "=a"(br[1]), "=a"(br[2]), "=a"(br[3]), "=a"(br[4]), "=a"(br[5]), "=a"(br[6]),
+                           "=a"(br[7]), "=&v"(tmp)
+                         : "s"(soff), "v"(rbase)
+                         : "memory");
+        };
+        // the first half landed (the second half's eight reads may still be in flight)
+        auto wait_b0 = [&](frag_t (&br)[8]) {
+            asm volatile("s_waitcnt lgkmcnt(8)"
+                         : "+a"(br[0]), "+a"(br[1]), "+a"(br[2]), "+a"(br[3]), "+a"(br[4]), "+a"(br[5]), "+a"(br[6]),
+                           "+a"(br[7])
+                         :
+                         : "memory");
+        };
+        const int qlane = 4 * (lane >> 4);
+        // epilogue lane bases: smem (+ the tile-word bytes, lane-independent), the
+        // row norm of this lane's column, this lane's first query in sig / ck1 / ck2
+        const uint32_t sbase = (uint32_t)(uintptr_t)smem;
+        const uint32_t nbase = sbase + 4u * (uint32_t)(lane & 15);
+        const uint32_t qbase = sbase + 4u * (uint32_t)qlane;
+        const uint32_t csoff = (uint32_t)((uintptr_t)sig - (uintptr_t)smem);
+        // +inf when one of this lane's queries is not fast-eligible (K1 > 2^50: a huge or
+        // non-finite query), so its elements always take the exact test
+        bool lane_force = false;
+#pragma unroll
+        for (int mq = 0; mq < 2; mq++)
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+                if (!(ck1[32 * w + 16 * mq + qlane + r] <= 0x1p50f)) lane_force = true;
+
+        acc_t acc[2][16];
+#pragma unroll
+        for (int mq = 0; mq < 2; mq++)
+#pragma unroll
+            for (int nr = 0; nr < 16; nr++) acc[mq][nr] = acc_t{0, 0, 0, 0};
+        frag_t b0[8], b1[8];
+        // one K block of one 16 x 16 tile: bf16 16x16x32, or (I8) int8 16x16x64 with exact int32 sums
+        auto mfma = [](const frag_t &x, const frag_t &y, const acc_t &c) -> acc_t {
+            if constexpr (I8)
+                return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, y, c, 0, 0, 0);
+            else
+                return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, y, c, 0, 0, 0);
+        };
+        // prologue: units 0 .. NB - 2 of the range (a unit = one K block of one row
+        // block; the ring holds K block ks of any row block in buffer ks % NB)
+#pragma unroll
+        for (int ks = 0; ks < NB - 1; ks++) load_stage(ks);
+        // unit 0 landed: the NB - 2 younger units outstanding
+        if (w == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, I8>(0, NB - 2, true)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(sd_younger<KBN, I8>(0, NB - 2, false)) : "memory");
+        raw_barrier();
+        read_half(0, 0, b0);
+        for (uint64_t blk = blk0; blk < blk1; blk++) {
+            sd_static_for<KBN>([&](auto KS) {
+                constexpr int ks = decltype(KS)::value;
+                read_half(ks, 1, b1);
+                wait_b0(b0);
+#pragma unroll
+                for (int mq = 0; mq < 2; mq++)
+#pragma unroll
+                    for (int nr = 0; nr < 8; nr++) acc[mq][nr] = mfma(areg[ks][mq], b0[nr], acc[mq][nr]);
+                wait_next(KS);  // the next unit landed
+                raw_barrier();  // (lgkmcnt(0): this wave's second-half reads done)
+#pragma unroll
+                for (int j = 0; j < 8; j++) asm volatile("" : "+a"(b1[j]));
+                // unit + 7 into the buffer of unit - 1 (fully read before this barrier)
+                load_stage((ks + NB - 1) % KBN);
+                if (ks + 1 < KBN) read_half(ks + 1, 0, b0);  // (the next block's first half: after the epilogue)
+#pragma unroll
+                for (int mq = 0; mq < 2; mq++)
+#pragma unroll
+                    for (int nr = 0; nr < 8; nr++) acc[mq][8 + nr] = mfma(areg[ks][mq], b1[nr], acc[mq][8 + nr]);
+            });
+            // The epilogue reads the accumulators through inline asm (agpr_read), which the
+            // compiler's hazard recognizer does not see: an MFMA's result may be read by a
+            // VALU op only after its passes + 2 wait states (XDL write -> VALU read; 11 for an
+            // 8-pass, 19 for a 16-pass op), so the block's last MFMAs get 24 here (the norm
+            // reads that come first usually cover them; this makes it unconditional).
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            // epilogue of row block blk (K3c's, over 16 row groups): C layout row
+            // (query) qlane + r, column (row) 16 nr + (lane & 15)
+            if constexpr (DIAG != 10) {
+                // Fast check per query group, then the exact test !(u < WS) (NaN-safe: a
+                // non-finite row or query always passes) on the groups the check could not
+                // rule out, survivors inserted into register-held lists (the slow path
+                // below).  Accumulators are read where they are used (agpr_read); every
+                // epilogue LDS access is inline asm with its own lgkmcnt wait (through C++
+                // the compiler cannot tell them from the stage ring's LDS DMA and waits
+                // vmcnt(0), draining the prefetch), at a lane base + an SGPR offset.
+                const uint32_t nsoff = (uint32_t)(NB * SD_STAGE + (blk & 1) * NSLOT);  // the block's norms
+                // row norms of row groups 8 hh .. 8 hh + 7 (hh 2, 3: I8's row errors, slot bytes 1280 ..)
+                auto read_norms8 = [&](int hh, float (&nrm)[8]) {
+                    uint32_t tmp;
+                    asm volatile("v_add_u32 %8, %9, %10\n\t"
+                                 "ds_read_b32 %0, %8\n\t"
+                                 "ds_read_b32 %1, %8 offset:64\n\t"
+                                 "ds_read_b32 %2, %8 offset:128\n\t"
+                                 "ds_read_b32 %3, %8 offset:192\n\t"
+                                 "ds_read_b32 %4, %8 offset:256\n\t"
+                                 "ds_read_b32 %5, %8 offset:320\n\t"
+                                 "ds_read_b32 %6, %8 offset:384\n\t"
+                                 "ds_read_b32 %7, %8 offset:448\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=v"(nrm[0]), "=v"(nrm[1]), "=v"(nrm[2]), "=v"(nrm[3]), "=v"(nrm[4]),
+                                   "=v"(nrm[5]), "=v"(nrm[6]), "=v"(nrm[7]), "=&v"(tmp)
+                                 : "s"(nsoff + (hh < 2 ? 512u * hh : 1280u + 512u * (hh - 2))), "v"(nbase)
+                                 : "memory");
+                };
+                auto read_consts = [&](int mq, float (&k1r)[4], float (&k2r)[4], float (&svr)[4]) {
+                    // sig, ck1, ck2 are consecutive 128-float arrays: one address, offsets 0 / 512 / 1024
+                    const uint32_t coff = (uint32_t)(csoff + 4 * (32 * w + 16 * mq));
+                    float4 k1v, k2v, sv;
+                    uint32_t tmp;
+                    asm volatile("v_add_u32 %3, %4, %5\n\t"
+                                 "ds_read_b128 %0, %3 offset:512\n\t"
+                                 "ds_read_b128 %1, %3 offset:1024\n\t"
+                                 "ds_read_b128 %2, %3\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=v"(k1v), "=v"(k2v), "=v"(sv), "=&v"(tmp)
+                                 : "s"(coff), "v"(qbase)
+                                 : "memory");
+                    k1r[0] = k1v.x, k1r[1] = k1v.y, k1r[2] = k1v.z, k1r[3] = k1v.w;
+                    k2r[0] = k2v.x, k2r[1] = k2v.y, k2r[2] = k2v.z, k2r[3] = k2v.w;
+                    svr[0] = sv.x, svr[1] = sv.y, svr[2] = sv.z, svr[3] = sv.w;
+                };
+                // (I8) B and the score scale of the lane's four queries of half mq: ckb, ccs at
+                // sig + 2048, + 2560
+                auto read_consts_i8 = [&](int mq, float (&kbr)[4], float (&csr)[4]) {
+                    const uint32_t coff = (uint32_t)(csoff + 4 * (32 * w + 16 * mq));
+                    float4 kbv, csv;
+                    uint32_t tmp;
+                    asm volatile("v_add_u32 %2, %3, %4\n\t"
+                                 "ds_read_b128 %0, %2 offset:2048\n\t"
+                                 "ds_read_b128 %1, %2 offset:2560\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=v"(kbv), "=v"(csv), "=&v"(tmp)
+                                 : "s"(coff), "v"(qbase)
+                                 : "memory");
+                    kbr[0] = kbv.x, kbr[1] = kbv.y, kbr[2] = kbv.z, kbr[3] = kbv.w;
+                    csr[0] = csv.x, csr[1] = csv.y, csr[2] = csv.z, csr[3] = csv.w;
+                };
+                (void)read_consts_i8;
+                if constexpr (DIAG == 16) n_blk++;
+                // fast check: the lane's 16 rows' largest norm bound bounds each of their E
+                // (E = fma(norm, K1q, K2q) is monotone in the norm), so per query the largest
+                // raw score of the lane's rows + that E against WS is a superset test of
+                // every element (monotone roundings); finite on the fast-eligible inputs
+                // (query K1 <= 2^50, row norms <= 2^60), else the exact test runs
+                float nmax, nsum;  // (nsum: NaN when a norm is -- fmaxf would drop it)
+                float hmin = 0.f;  // (L2) the h of the lane's smallest norm: the most favourable of its 16 rows
+                {
+                    float n0[8], n1[8];
+                    read_norms8(0, n0);
+                    read_norms8(1, n1);
+                    nmax = n0[0];
+                    nsum = n0[0];
+#pragma unroll
+                    for (int j2 = 1; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n0[j2]), nsum += n0[j2];
+#pragma unroll
+                    for (int j2 = 0; j2 < 8; j2++) nmax = __builtin_fmaxf(nmax, n1[j2]), nsum += n1[j2];
+                    if constexpr (L2) {
+                        float nmin = n0[0];
+#pragma unroll
+                        for (int j2 = 1; j2 < 8; j2++) nmin = __builtin_fminf(nmin, n0[j2]);
+#pragma unroll
+                        for (int j2 = 0; j2 < 8; j2++) nmin = __builtin_fminf(nmin, n1[j2]);
+                        hmin = (nmin * nmin) * hg;  // (finite where the check decides: nmax <= 2^60, no NaN)
+                    }
+                }
+                // (I8) the lane's 16 rows' largest error bound: E = fma(err, A, fma(norm, B, K2))
+                // is monotone in both
+                float emx = 0.f, esum = 0.f;
+                if constexpr (I8) {
+                    float e0[8], e1[8];
+                    read_norms8(2, e0);
+                    read_norms8(3, e1);
+                    emx = e0[0];
+                    esum = e0[0];
+#pragma unroll
+                    for (int j2 = 1; j2 < 8; j2++) emx = __builtin_fmaxf(emx, e0[j2]), esum += e0[j2];
+#pragma unroll
+                    for (int j2 = 0; j2 < 8; j2++) emx = __builtin_fmaxf(emx, e1[j2]), esum += e1[j2];
+                }
+                // per (query half mq, query r of the lane's four): whether some lane cannot rule
+                // out its 16 elements -- only those groups run the exact test (a wave-uniform
+                // bit each; typically one or two of the eight)
+                const bool force = lane_force || !(nmax <= 0x1p60f) || nsum != nsum || !(emx <= 0x1p60f) || esum != esum;
+                uint32_t wact = 0;
+#pragma unroll
+                for (int mq = 0; mq < 2; mq++) {
+                    float k1r[4], k2r[4], svr[4];
+                    read_consts(mq, k1r, k2r, svr);
+                    if constexpr (I8) {
+                        // the largest exact int32 score, scaled once (rounding is monotone)
+                        float kbr[4], csr[4];
+                        read_consts_i8(mq, kbr, csr);
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            int mi = agpr_read(acc[mq][0][r]);
+#pragma unroll
+                            for (int nr = 1; nr < 16; nr++) mi = max(mi, agpr_read(acc[mq][nr][r]));
+                            const float m = (float)mi * csr[r];
+                            const float t =
+                                sc_u<L2>(m, __builtin_fmaf(emx, k1r[r], __builtin_fmaf(nmax, kbr[r], k2r[r])), hmin) -
+                                svr[r];
+                            if (__ballot(force || t >= 0.f)) wact |= 1u << (4 * mq + r);
+                        }
+                        continue;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        float m = agpr_read(acc[mq][0][r]);
+#pragma unroll
+                        for (int nr = 1; nr < 16; nr++) m = __builtin_fmaxf(m, agpr_read(acc[mq][nr][r]));
+                        const float t = (m + __builtin_fmaf(nmax, k1r[r], k2r[r])) - svr[r];
+                        if (__ballot(force || t >= 0.f)) wact |= 1u << (4 * mq + r);
+                    }
+                }
+                const bool slow = wact != 0 && DIAG != 4;
+                if (slow) {
+                    uint64_t vm[4];
+                    {
+                        uint4 vw0, vw1, aw0, aw1;
+                        uint32_t tmp;
+                        asm volatile("v_add_u32 %4, %5, %6\n\t"
+                                     "ds_read_b128 %0, %4 offset:1024\n\t"
+                                     "ds_read_b128 %1, %4 offset:1040\n\t"
+                                     "ds_read_b128 %2, %4 offset:1056\n\t"
+                                     "ds_read_b128 %3, %4 offset:1072\n\t"
+                                     "s_waitcnt lgkmcnt(0)"
+                                     : "=v"(vw0), "=v"(vw1), "=v"(aw0), "=v"(aw1), "=&v"(tmp)
+                                     : "s"(nsoff), "v"(sbase)
+                                     : "memory");
+                        const uint64_t words[4] = {((uint64_t)vw0.y << 32) | vw0.x, ((uint64_t)vw0.w << 32) | vw0.z,
+                                                   ((uint64_t)vw1.y << 32) | vw1.x, ((uint64_t)vw1.w << 32) | vw1.z};
+                        const uint64_t allows[4] = {((uint64_t)aw0.y << 32) | aw0.x, ((uint64_t)aw0.w << 32) | aw0.z,
+                                                    ((uint64_t)aw1.y << 32) | aw1.x, ((uint64_t)aw1.w << 32) | aw1.z};
+#pragma unroll
+                        for (int h = 0; h < 4; h++) {
+                            vm[h] = sc_tile_mask(a, a.tile_begin + blk * 4 + h, words[h], allows[h]);
+                        }
+                    }
+                    const uint64_t slot0 = (a.tile_begin + blk * 4) * 64;
+                    if constexpr (DIAG == 16) n_slow++;
+                    // Per active group gi = (mq, r): lane l tests its column's 16 rows against
+                    // query ql = 16 mq + r + qlane (C layout), and row l >> 4 of the register v
+                    // holds that same query's list (lane l: entry l & 15) -- the four queries of
+                    // the group, one per 16-lane row.  A survivor is inserted into its own row in
+                    // registers (DPP shift), the row's thresholds tighten at once, and the lists
+                    // and thresholds go back to LDS once per group.  The group loop is not
+                    // unrolled (the code would not fit the unroller's budget); its 16
+                    // accumulator elements come out of the AGPRs through one switch.
+                    float nrm16[16];
+                    read_norms8(0, *reinterpret_cast<float(*)[8]>(&nrm16[0]));
+                    read_norms8(1, *reinterpret_cast<float(*)[8]>(&nrm16[8]));
+                    float err16[I8 ? 16 : 1];  // (I8) the rows' error bounds
+                    if constexpr (I8) {
+                        read_norms8(2, *reinterpret_cast<float(*)[8]>(&err16[0]));
+                        read_norms8(3, *reinterpret_cast<float(*)[8]>(&err16[8]));
+                    }
+                    for (uint32_t gw = wact; gw; gw &= gw - 1) {
+                        const int gi = __builtin_ctz(gw);
+                        if constexpr (DIAG == 16) n_grp++;
+                        float uv[16];  // (I8: the exact int32 scores, exactly as floats: |score| < 2^24)
+                        switch (gi) {
+#define WVG_SD_GROUP(G)                                                                        \
+    case G:                                                                                    \
+        _Pragma("unroll") for (int nr = 0; nr < 16; nr++) uv[nr] = (float)agpr_read(acc[(G) >> 2][nr][(G) & 3]); \
+        break;
+                        WVG_SD_GROUP(0) WVG_SD_GROUP(1) WVG_SD_GROUP(2) WVG_SD_GROUP(3)
+                        WVG_SD_GROUP(4) WVG_SD_GROUP(5) WVG_SD_GROUP(6) WVG_SD_GROUP(7)
+#undef WVG_SD_GROUP
+                        default: break;
+                        }
+                        const uint32_t ql = 16u * (uint32_t)(gi >> 2) + (uint32_t)(gi & 3) + (uint32_t)qlane;
+                        const uint32_t la = S.laddr + ql * (SCREEN_M * 8) + 8u * (uint32_t)(lane & 15);
+                        const uint32_t ta = tbase + 4u * ql;  // tau; sig + 512, ck1 + 1024, ck2 + 1536, cem + 2048
+                        uint2 v2;
+                        float wt, ws, em, k1, k2;
+                        asm volatile("ds_read_b64 %0, %6\n\t"
+                                     "ds_read_b32 %1, %7\n\t"
+                                     "ds_read_b32 %2, %7 offset:512\n\t"
+                                     "ds_read_b32 %3, %7 offset:2048\n\t"
+                                     "ds_read_b32 %4, %7 offset:1024\n\t"
+                                     "ds_read_b32 %5, %7 offset:1536\n\t"
+                                     "s_waitcnt lgkmcnt(0)"
+                                     : "=v"(v2), "=v"(wt), "=v"(ws), "=v"(em), "=v"(k1), "=v"(k2)
+                                     : "v"(la), "v"(ta)
+                                     : "memory");
+                        float kbq = 0.f, csq = 1.f;  // (I8) B and the score scale: ckb + 2560, ccs + 3072
+                        if constexpr (I8)
+                            asm volatile("ds_read_b32 %0, %2 offset:2560\n\t"
+                                         "ds_read_b32 %1, %2 offset:3072\n\t"
+                                         "s_waitcnt lgkmcnt(0)"
+                                         : "=v"(kbq), "=v"(csq)
+                                         : "v"(ta)
+                                         : "memory");
+                        float cqq = 0.f;  // (L2) Cq: ccq + 3584
+                        if constexpr (L2)
+                            asm volatile("ds_read_b32 %0, %1 offset:3584\n\t"
+                                         "s_waitcnt lgkmcnt(0)"
+                                         : "=v"(cqq)
+                                         : "v"(ta)
+                                         : "memory");
+                        uint64_t v = ((uint64_t)v2.y << 32) | v2.x;
+                        const int li = lane & 15;
+#pragma unroll
+                        for (int nr = 0; nr < 16; nr++) {
+                            const uint64_t m64 = ((vm[nr >> 2] >> (16 * (nr & 3))) & 0xFFFFull) * 0x0001000100010001ull;
+                            float u;
+                            if constexpr (L2)  // (h: NaN beyond the norm limit, so the row is a candidate)
+                                u = sc_u<true>(uv[nr] * csq,
+                                               __builtin_fmaf(err16[nr], k1, __builtin_fmaf(nrm16[nr], kbq, k2)),
+                                               nrm16[nr] <= 0x1p60f ? (nrm16[nr] * nrm16[nr]) * hg : __builtin_nanf(""));
+                            else if constexpr (I8)
+                                u = uv[nr] * csq + __builtin_fmaf(err16[nr], k1, __builtin_fmaf(nrm16[nr], kbq, k2));
+                            else
+                                u = uv[nr] + __builtin_fmaf(nrm16[nr], k1, k2);
+                            uint64_t pass = __ballot(!(u < ws)) & m64;
+                            while (pass) {
+                                const int j = __builtin_ctzll(pass);
+                                pass &= pass - 1;
+                                const int g = j >> 4;
+                                const float uj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), j));
+                                const float cqg = L2 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cqq), j)) : 0.f;
+                                const float lower = L2 ? sc_lower_l2(uj, cqg) : sc_lower(uj, cosine);
+                                float wtg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wt), j));
+                                if (!(lower <= wtg)) continue;
+                                if constexpr (DIAG == 16) n_call++;
+                                const uint64_t key = ((uint64_t)wvg_ord_f32(lower) << 32) |
+                                                     (uint32_t)(slot0 + 16u * (uint32_t)nr + (uint32_t)(j & 15));
+                                if (!(key < readlane64(v, 16 * g + SCREEN_M - 1))) continue;
+                                const bool inrow = (lane >> 4) == g;
+                                const int pos = __popcll(__ballot(inrow && v < key));
+                                const uint64_t sh = row_shr1_64(v);
+                                v = inrow ? (li > pos ? sh : (li == pos ? key : v)) : v;
+                                const uint64_t nk = readlane64(v, 16 * g + K - 1);
+                                const uint64_t nm = readlane64(v, 16 * g + SCREEN_M - 1);
+                                const float emg = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(em), j));
+                                if (nk != WVG_KEY_NONE) wtg = fminf(wtg, sc_tau_k(key_lower(nk), emg, cosine));
+                                if (nm != WVG_KEY_NONE) wtg = fminf(wtg, key_lower(nm));
+                                const float wsg = L2 ? sc_sigma_l2(wtg, cqg) : sc_sigma(wtg, cosine);
+                                wt = inrow ? wtg : wt;
+                                ws = inrow ? wsg : ws;
+                                // the row's other survivors of this element group meet the new threshold
+                                pass &= ~(0xFFFFull << (16 * g)) | __ballot(!(u < ws));
+                            }
+                        }
+                        const uint2 o2 = make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+                        asm volatile("ds_write_b64 %0, %1" ::"v"(la), "v"(o2) : "memory");
+                        if (li == 0)
+                            asm volatile("ds_write_b32 %0, %1\n\t"
+                                         "ds_write_b32 %0, %2 offset:512" ::"v"(ta), "v"(wt), "v"(ws)
+                                         : "memory");
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
+            } else {
+                // diagnostic (DIAG 10): the stage loop alone -- the accumulators are consumed by
+                // one sum, so the MFMAs stay (without any consumer the compiler removes them)
+                float x = 0.f;
+#pragma unroll
+                for (int mq = 0; mq < 2; mq++)
+#pragma unroll
+                    for (int nr = 0; nr < 16; nr++) x += (float)agpr_read(acc[mq][nr][0]);
+                if (x == 0x1p-120f) a.partials[0] = 0;
+            }
+#pragma unroll
+            for (int mq = 0; mq < 2; mq++)
+#pragma unroll
+                for (int nr = 0; nr < 16; nr++) acc[mq][nr] = acc_t{0, 0, 0, 0};
+            // the next block's first K block: its stage landed before the last barrier and is not
+            // overwritten before the next block's second barrier
+            read_half(0, 0, b0);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef WVG_TOOLS
+    if constexpr (DIAG == 16) {
+        if (lane == 0) {
+            atomicAdd(&g_screen_ctr[0], (unsigned long long)n_blk);
+            atomicAdd(&g_screen_ctr[1], (unsigned long long)n_slow);
+            atomicAdd(&g_screen_ctr[2], (unsigned long long)n_call);
+            atomicAdd(&g_screen_ctr[3], (unsigned long long)n_grp);
+        }
+    }
+#endif
+    __syncthreads();
+    // each wave owns whole lists: its 32 queries' range lists go straight to partials
+    for (int ql = 0; ql < 32; ql++) {
+        const uint32_t q = q0 + (uint32_t)(32 * w + ql);
+        if (q >= a.nq) break;
+        const uint64_t x = lane < M ? lists[((size_t)w * 32 + ql) * M + lane] : WVG_KEY_NONE;
+        uint64_t *out = a.partials + ((size_t)q * a.nrr + rr) * M;
+        if (lane < M) out[lane] = x;
+        if (lane == K - 1 && x != WVG_KEY_NONE) {
+            const float t = sc_tau_k(key_lower(x), cem[32 * w + ql], cosine);
+            atomicMin(a.gbound + q, wvg_ord_f32(t));
+        }
+    }
+}
+
+template <int KBN>
+__global__ WVG_NO_PK_F32 __launch_bounds__(SD_WAVES * 64, 1) void screen_ar_l2_kernel(ScreenL2I8Args a)
+{
+    screen_ar_l2_body<KBN>(a.l.s, a.l.cq, a.l.hg);
+}
+
+// K3i-L2's per-query constants, one wave per query: K3i's Sq, A (k1), B (kb),
+// K2 (k2), score scale (css) and 1 / Sq (qinv), and K3c-L2's Cq with the l2
+// Emax_q = E_tot at the corpus maxima of Ex and Nx -- all from fp64 sums,
+// rounded to the safe side.  A query that is not finite, whose scale leaves
+// the normal range or whose norm bound is above 2^56: A = +inf, Cq = -inf.
+__global__ __launch_bounds__(256) void screen_qconst_l2_i8_kernel(const float *q, uint32_t nq, uint32_t qpitch,
+                                                                  uint32_t dim, uint32_t nq_pad, const uint32_t *mx,
+                                                                  const float *scale, float *k1, float *k2, float *kb,
+                                                                  float *css, float *qinv, float *emax, float *cq)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t qi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (qi >= nq_pad) return;
+    float amax = 0.f;
+    bool bad = false;
+    if (qi < nq)
+        for (uint32_t i = lane; i < dim; i += 64) {
+            const float a = __builtin_fabsf(q[(size_t)qi * qpitch + i]);
+            if (a <= 3.4028235e38f) amax = __builtin_fmaxf(amax, a);
+            else bad = true;
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) amax = __builtin_fmaxf(amax, __shfl_xor(amax, off));
+    bad = __ballot(bad) != 0;
+    const float sq = amax > 0.f ? amax / 127.f : 1.f, inv = 1.f / sq;
+    double st = 0.0, se = 0.0, sn = 0.0;
+    if (qi < nq)
+        for (uint32_t i = lane; i < dim; i += 64) {
+            const float x = q[(size_t)qi * qpitch + i];
+            const double t = (double)sq * (double)si_code(x, inv);
+            st += t * t;
+            se += ((double)x - t) * ((double)x - t);
+            sn += (double)x * x;
+        }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        st += __shfl_xor(st, off);
+        se += __shfl_xor(se, off);
+        sn += __shfl_xor(sn, off);
+    }
+    if (lane) return;
+    const double nqt = norm_upper(st), eq = norm_upper(se);
+    const float nqu = norm_upper(sn);
+    float A = (float)(nqt * (1.0 + 0x1p-19) + 0x1p-120);
+    float B = (float)(eq * (1.0 + 0x1p-19) + 4.0 * dim * 0x1p-24 * (double)nqu + 0x1p-19 * nqt + 0x1p-120);
+    float K2 = (float)(0x1p-120 * (double)nqu + 0x1p-110);
+    float C = (float)(sn * (1.0 - 0x1p-19 - screen_l2_alpha(dim)) - 0x1p-100);
+    float cs = scale[0] * sq;
+    if (bad || !(cs >= 0x1p-100f && cs <= 0x1p100f) || !(A < __builtin_inff()) || !(nqu <= 0x1p56f)) {
+        A = __builtin_inff();
+        C = -__builtin_inff();
+    }
+    const double beta = screen_l2_alpha(dim) + 0x1p-18;
+    const float nm = __uint_as_float(mx[0]);
+    const double e1 = __builtin_fmaf(__uint_as_float(mx[1]), A, __builtin_fmaf(nm, B, K2));
+    float E = (float)((2.0 * e1 + beta * ((double)nqu * nqu + (double)nm * nm) + 0x1p-99) * (1.0 + 0x1p-20));
+    if (qi >= nq) A = B = K2 = cs = C = E = 0.f;
+    k1[qi] = A;
+    k2[qi] = K2;
+    kb[qi] = B;
+    css[qi] = cs;
+    qinv[qi] = inv;
+    emax[qi] = E;
+    cq[qi] = C;
 }
 
 // ---------------------------------------------------------------------------
@@ -2422,6 +3162,8 @@ struct ScreenKernel {
     int diag;
     void (*fn)(ScreenArgs);
     uint32_t lds, threads;  // dynamic LDS bytes, workgroup size
+    bool l2 = false;        // K3i-L2: fn_l2 instead of fn
+    void (*fn_l2)(ScreenL2I8Args) = nullptr;
 };
 static const ScreenKernel SCREEN_KERNELS[] = {
     {false, 0, SL_K3C, 0, &screen_kernel, SC_LDS, SC_WAVES * 64},
@@ -2432,6 +3174,9 @@ static const ScreenKernel SCREEN_KERNELS[] = {
     {true, 16, SL_1X4, 0, &screen_ar_kernel<16, 0, true>, si_lds(si_nbuf(16)), SD_WAVES * 64},
     {true, 8, SL_2X2, 0, &screen_i8_kernel<8>, SJ_LDS, SD_WAVES * 64},
     {true, 12, SL_2X2, 0, &screen_i8_kernel<12>, SJ_LDS, SD_WAVES * 64},
+    {true, 8, SL_2X2, 0, nullptr, SJ_LDS_L2, SD_WAVES * 64, true, &screen_i8_l2_kernel<8>},
+    {true, 12, SL_2X2, 0, nullptr, SJ_LDS_L2, SD_WAVES * 64, true, &screen_i8_l2_kernel<12>},
+    {true, 16, SL_1X4, 0, nullptr, si_lds_l2(si_nbuf(16)), SD_WAVES * 64, true, &screen_ar_l2_kernel<16>},
 #ifdef WVG_TOOLS  // Tuning::screen_diag: 4 = no exact path, 10 = the stage loop alone, 16 = counters
     {false, 24, SL_1X4, 4, &screen_ar_kernel<24, 4>, SD_LDS, SD_WAVES * 64},
     {false, 24, SL_1X4, 10, &screen_ar_kernel<24, 10>, SD_LDS, SD_WAVES * 64},
@@ -2446,19 +3191,22 @@ static const ScreenKernel SCREEN_KERNELS[] = {
 // The kernel of a launch: K3i on an int8 shadow -- 2 x 2 waves for d = 512 /
 // 768, K3d's 1 x 4 layout for d = 1024 (64 resident queries would not fit the
 // registers) or on request (variant 5); else K3d where its template applies
-// (and variant is not 1), else K3c.  nullptr: no such kernel (a variant or
-// diagnostic that this build or this (int8, kbn) does not have).
-static const ScreenKernel *pick_screen_kernel(bool i8, uint32_t kbn, int variant, int diag)
+// (and variant is not 1), else K3c.  l2 (an l2-squared corpus on an int8
+// shadow): K3i-L2 in the same two layouts, whatever the variant.  nullptr: no
+// such kernel (a variant or diagnostic that this build or this (int8, kbn)
+// does not have).
+static const ScreenKernel *pick_screen_kernel(bool i8, uint32_t kbn, int variant, int diag, bool l2 = false)
 {
     // every kernel's dynamic-LDS limit, once
     static const bool attr = [] {
         bool ok = true;
         for (const ScreenKernel &k : SCREEN_KERNELS)
-            ok &= hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)k.lds) == hipSuccess;
+            ok &= hipFuncSetAttribute(k.l2 ? reinterpret_cast<const void *>(k.fn_l2) : reinterpret_cast<const void *>(k.fn),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) == hipSuccess;
         return ok;
     }();
     (void)attr;
+    if (l2) variant = 0;
     if (variant != 0 && variant != (i8 ? 5 : 1)) return nullptr;
     ScreenLayout layout;
     if (i8)
@@ -2467,33 +3215,41 @@ static const ScreenKernel *pick_screen_kernel(bool i8, uint32_t kbn, int variant
         layout = variant == 1 || (kbn != 16 && kbn != 24) ? SL_K3C : SL_1X4;
     if (layout == SL_K3C) kbn = 0;
     for (const ScreenKernel &k : SCREEN_KERNELS)
-        if (k.i8 == i8 && k.kbn == kbn && k.layout == layout && k.diag == diag) return &k;
+        if (k.i8 == i8 && k.kbn == kbn && k.layout == layout && k.diag == diag && k.l2 == l2) return &k;
     return nullptr;
 }
 
 hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
 {
-    const bool i8 = !L.l2 && L.i8 && screen_i8_supported(L.dim);  // (an l2-squared corpus has the bf16 shadow)
+    const bool i8 = L.i8 && screen_i8_supported(L.dim);  // (l2-squared: only under batch_screen = 3, K3i-L2)
     const uint32_t kbn = i8 ? L.dim / 64 : screen_kblocks(L.dim, L.l2);  // (K3i: 64-deep int8 K blocks)
+    const bool l2c = L.l2 && !i8;  // K3c-L2 (the bf16 shadow)
     const uint32_t nq_pad = (L.nq + SC_BQ - 1) / SC_BQ * SC_BQ, nqb = nq_pad / SC_BQ;
     hipError_t e;
     // the kernel first: an unsupported (variant, diag) starts nothing
-    // (l2-squared: K3c-L2 whatever the variant; a diagnostic has no L2 form)
-    const ScreenKernel *sk = L.l2 ? pick_screen_kernel(false, kbn, 1, 0)
-                                  : pick_screen_kernel(i8, kbn, tuning().screen_variant, tuning().screen_diag);
+    // (l2-squared: K3c-L2 or K3i-L2 whatever the variant; a diagnostic has no L2 form)
+    const ScreenKernel *sk = l2c    ? pick_screen_kernel(false, kbn, 1, 0)
+                             : L.l2 ? pick_screen_kernel(true, kbn, 0, 0, true)
+                                    : pick_screen_kernel(i8, kbn, tuning().screen_variant, tuning().screen_diag);
     if (!sk || (L.l2 && (tuning().screen_diag != 0 || !L.cq))) return hipErrorInvalidValue;
     void (*const kern)(ScreenArgs) = sk->fn;
-    const uint32_t lds = L.l2 ? (uint32_t)SC_LDS_L2 : sk->lds, threads = sk->threads;
-    if (L.l2) {
+    const uint32_t lds = l2c ? (uint32_t)SC_LDS_L2 : sk->lds, threads = sk->threads;
+    if (l2c) {
         static const bool attr_l2 =
             hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_l2_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_L2) == hipSuccess;
         (void)attr_l2;
     }
-    // one launch of the chosen kernel over the ranges in x (K3c-L2 wraps x with Cq and hg)
+    // one launch of the chosen kernel over the ranges in x (K3c-L2 and K3i-L2 wrap x with Cq and hg)
     const float hg = L.l2 ? screen_l2_hg(L.dim) : 0.f;
     auto launch = [&](const ScreenArgs &x, uint32_t blocks, hipEvent_t e0, hipEvent_t e1) {
-        if (L.l2) {
+        if (L.l2 && i8) {
+            const ScreenL2I8Args xl{{x, L.cq, hg}};
+            if (e0 || e1)
+                hipExtLaunchKernelGGL(sk->fn_l2, dim3(blocks), dim3(threads), lds, s, e0, e1, 0u, xl);
+            else
+                hipLaunchKernelGGL(sk->fn_l2, dim3(blocks), dim3(threads), lds, s, xl);
+        } else if (L.l2) {
             const ScreenL2Args xl{x, L.cq, hg};
             if (e0 || e1)
                 hipExtLaunchKernelGGL(screen_l2_kernel, dim3(blocks), dim3(threads), lds, s, e0, e1, 0u, xl);
@@ -2505,7 +3261,15 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
             hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, s, x);
         }
     };
-    if (L.l2) {
+    if (L.l2 && i8) {
+        // K3i-L2: K3i's constants with Cq and the l2 Emax_q from one kernel, then the int8 fragments
+        hipLaunchKernelGGL(screen_qconst_l2_i8_kernel, dim3(nq_pad / 4), dim3(256), 0, s, L.queries, L.nq, L.qpitch,
+                           L.dim, nq_pad, L.nmax, reinterpret_cast<const float *>(L.nmax + 2), L.k1, L.k2, L.kb, L.css,
+                           L.qinv, L.emax, L.cq);
+        hipLaunchKernelGGL(screen_qfrag_i8_kernel, dim3((unsigned)(((uint64_t)nq_pad / 16 * kbn * 64 + 255) / 256)),
+                           dim3(256), 0, s, L.queries, L.nq, L.qpitch, L.dim, kbn, nq_pad / 16, L.qinv,
+                           reinterpret_cast<uint4 *>(L.qfrag));
+    } else if (L.l2) {
         hipLaunchKernelGGL(screen_qfrag_kernel, dim3((unsigned)(((uint64_t)nq_pad / 16 * kbn * 64 + 255) / 256)),
                            dim3(256), 0, s, L.queries, L.nq, L.qpitch, L.dim, kbn, nq_pad / 16,
                            reinterpret_cast<uint4 *>(L.qfrag));

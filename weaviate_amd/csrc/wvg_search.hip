@@ -269,7 +269,8 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
         p.groups = pq_cosched_groups(p.mq ? (nq + p.mq - 1) / p.mq : nq,
                                      std::max(scan_groups_for(a1, c->ctx->num_cus), 8));
     }
-    // K3c-L2: an l2-squared batch takes the bf16 screen + exact rescore exactly when a dot batch of
+    // K3c-L2 / K3i-L2 (the corpus's shadow decides: int8 only under batch_screen = 3): an l2-squared
+    // batch takes the screen + exact rescore exactly when a dot batch of
     // the same shape would take K3c (a batch: nq >= 2).  There is no K3b for l2-squared, so the plan
     // above -- the co-scheduled K1 / K1Q -- stays as the path of a shadow that cannot be used.
     if (gemm_ok && c->kind == WVG_KIND_F32 && c->metric == WVG_METRIC_L2 && mn > 0 && nq >= mn && nq >= 2 &&
@@ -285,6 +286,8 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
         ScanArgs a1 = a;
         a1.nq = 1;
         p.fb_groups = (uint32_t)std::min(scan_groups_for(a1, c->ctx->num_cus), c->ctx->num_cus);
+        // (K3i-L2's int8 fragments take dim / 64 blocks of the same size; the workspace keeps the bf16
+        // count, as a dot corpus's does: a plan made before the shadow exists must hold the bf16 fallback)
         p.kbn = screen_kblocks(c->dim, true);
     }
     return p;
@@ -1537,9 +1540,7 @@ int wvg_search_batch_plan(wvg_corpus *c, uint32_t nq, uint32_t k, int shared_all
     out->matrix = p.gemm || p.screen;
     if (p.screen) {
         // the shadow a first screened search would build (ensure_shadow), or the one that exists
-        const bool i8 = c->d_shadow ? c->sh_i8
-                                    : c->ctx->opt.batch_screen == 2 && c->metric != WVG_METRIC_L2 &&
-                                          screen_i8_supported(c->dim);
+        const bool i8 = c->d_shadow ? c->sh_i8 : shadow_wants_i8(c);
         out->screen = i8 ? 2u : 1u;
         out->shadow_bytes_per_row = i8 ? c->dim + 8 : 64 * screen_kblocks(c->dim, c->metric == WVG_METRIC_L2) + 4;
     }

@@ -26,7 +26,10 @@ def device_count() -> int:
 class Context:
     """wvg_open_ex / wvg_close.  Keyword options set the fields of
     wvg_options (mfma_min_queries, cache_reuse, merge_wait_us, batch_screen);
-    the others keep wvg_options_default's values."""
+    the others keep wvg_options_default's values.  batch_screen: 2 (default)
+    int8 / bf16 screen for dot / cosine batches and the bf16 screen for
+    l2-squared ones, 1 bf16 everywhere, 0 exact only, 3 as 2 with the int8
+    screen for l2-squared batches at d = 512 / 768 / 1024 too (K3i-L2)."""
 
     def __init__(self, device: int = 0, **options):
         self.lib = _lib.load()

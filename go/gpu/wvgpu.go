@@ -170,7 +170,7 @@ func Open(device int) (*Ctx, error) {
 // zero value turns the feature off.  OpenWith(dev, nil) = the defaults.
 type Options struct {
 	MFMAMinQueries uint32 // dot / cosine batches of at least this many queries use MFMA (default 32)
-	CacheReuse     int32  // 1: consecutive scans reuse the Infinity Cache (default); 0: streaming
+	CacheReuse     int32  // 1: consecutive scans reuse the Infinity Cache (default); 0: streaming; 2: as 1, and PQ codebooks beyond LDS (m >= 96 at ks = 256) share code reads slice-wise in pipelined calls
 	MergeWaitUs    uint32 // query-stream merge wait bound (default 4 s)
 	BatchScreen    int32  // 2: int8 screen (d 512/768/1024, else bf16) + exact rescore (default); 1: bf16; 0: exact only; 3 (opt-in): as 2, and l2-squared batches at d 512/768/1024 take the int8 screen too
 	Coalesce       int32  // 1: concurrent single-query searches of a corpus share launches (default)
@@ -987,7 +987,8 @@ type StreamPlan struct {
 // DevicePipelinedPlan: the StreamPlan of a call with nq queries and k results
 // each.  Host only: nothing is launched.  F32, BQ and PQ corpora (BQ: 8 queries per
 // pass for nq >= 2 with cache_reuse on, never seeded or screened; PQ: 4 per pass up
-// to m = 32 at ks = 256, 2 up to m = 64, one scan per query beyond; a PQ corpus
+// to m = 32 at ks = 256, 2 up to m = 64, beyond that one scan per query, or 4 per
+// pass through the slice-wise scan in a context with CacheReuse = 2; a PQ corpus
 // without a codebook is unsupported).
 func (x *Corpus) DevicePipelinedPlan(nq, k int) (StreamPlan, error) {
 	defer pin(x)()

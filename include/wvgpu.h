@@ -84,7 +84,10 @@ typedef struct wvg_options {
                                   wvg_search_device_pipelined call share each row read.  0: streaming --
                                   one direction, non-temporal loads, no reuse between scans: one full scan
                                   per query (e.g. next to other memory-heavy work, or to measure the
-                                  DRAM-bound rate). */
+                                  DRAM-bound rate).  2: as 1, and the queries of a pipelined call on a PQ
+                                  corpus whose LUTs do not fit LDS two at a time (m >= 96 at ks = 256)
+                                  share their code reads too, 4 to a pass, through a slice-wise LUT
+                                  image (wvg_search_device_pipelined); same results, same workspace. */
     uint32_t merge_wait_us;    /* bound on the in-launch merge's wait for one query's scan workgroups
                                   (wvg_search_device_pipelined); 0 = the default, 4 s.  On expiry the
                                   query gets empty results and wvg_search_device_check fails. */
@@ -420,9 +423,14 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
  * queries' entries side by side, then the merge of the partial lists; no
  * workgroup waits for another and the status block is not touched.  Every
  * query's sum runs in segment order from 0, so per query the result is
- * wvg_search_device's for that query alone, bit for bit.  One query,
- * cache_reuse = 0 or a larger codebook (m >= 96 at ks = 256) is
- * wvg_search_device's route for that nq.  A PQ corpus whose codebook has not
+ * wvg_search_device's for that query alone, bit for bit.  A larger codebook
+ * (m >= 96 at ks = 256) in a context with cache_reuse = 2 takes the same
+ * three launches with Q = 4 and a scan whose image holds a slice of S
+ * consecutive segments at a time (S = 32 at ks = 256): a wave carries the
+ * partial sums of a block of tiles in registers from slice to slice, still
+ * in segment order, so the results are again wvg_search_device's bit for
+ * bit.  One query, cache_reuse = 0, or such a codebook under cache_reuse = 1
+ * is wvg_search_device's route for that nq.  A PQ corpus whose codebook has not
  * been set has no (m, ks) and hence no route: WVG_ERR_UNSUPPORTED from this
  * call, the filtered one and the plan, checked before anything else about
  * the corpus (wvg_search_device answers WVG_ERR_INVALID, as before).
@@ -514,8 +522,9 @@ int wvg_search_device_bq_rescore(wvg_corpus *bq, wvg_corpus *f32, const float *d
  * ceil(nq / Q), 0, 0} with the scan's Q (8) for nq >= 2 and cache_reuse on,
  * {0, 1, nq, 0, 0} otherwise.  A PQ corpus: {1, Q, ceil(nq / Q), 0, 0} with
  * the scan's Q (4 or 2 by how many of its LUTs fit LDS for this k) for nq
- * >= 2 and cache_reuse on, {0, 1, nq, 0, 0} otherwise, a codebook beyond
- * the shared scan (m >= 96 at ks = 256) included.  Errors as the search's
+ * >= 2 and cache_reuse on, {0, 1, nq, 0, 0} otherwise; a codebook beyond
+ * the whole image (m >= 96 at ks = 256) is {1, 4, ceil(nq / 4), 0, 0} for nq
+ * >= 2 under cache_reuse = 2 and {0, 1, nq, 0, 0} under 1.  Errors as the search's
  * (a PQ corpus without a codebook, k > 256, an F32 corpus with dim % 4 !=
  * 0).                                                                       */
 typedef struct wvg_stream_plan {

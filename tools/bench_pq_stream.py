@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The device query stream of PQ corpora against the calls it replaces: random PQ codes
-(--configs rows x m x k at dim 128 and ks = 256; default 100M x 32 at k = 10 and k = 100,
-100M x 64, 10M x 32 and 1M x 32), --batch queries (default 16) per call.  Per configuration,
+(--configs rows x m x k at ks = 256, dim 128 where m divides it and 4 m otherwise; default 100M x 32
+at k = 10 and k = 100, 100M x 64, 10M x 32 and 1M x 32), --batch queries (default 16) per call.
+--cache-reuse sets the context's wvg_options.cache_reuse: 2 sends m >= 96 through the slice form of
+the shared-row scan, 1 (default) leaves those on wvg_search_device's route.  Per configuration,
 us per call of
 
   pipelined       wvg_search_device_pipelined, one call of 16 queries (the shared-row scan)
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--lib", default=os.path.join(ROOT, "weaviate_amd", "libwvgpu.so"))
     ap.add_argument("--configs", default="100000000x32x10,100000000x32x100,100000000x64x10,10000000x32x10,1000000x32x10")
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--cache-reuse", type=int, default=1, choices=(0, 1, 2))
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -62,17 +65,18 @@ def main():
     dev = torch.device("cuda:0")
     nq = args.batch
     configs = [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]
-    with dev_mod.Context(0) as ctx:
+    with dev_mod.Context(0, cache_reuse=args.cache_reuse) as ctx:
         lib = ctx.lib
         stream = torch.cuda.current_stream().cuda_stream
         corpus, shape = None, None
         for n, m, k in configs:
+            dim = DIM if DIM % m == 0 else 4 * m
             if shape != (n, m):  # consecutive configurations of one shape share the corpus
                 if corpus is not None:
                     corpus.destroy()
                     torch.cuda.empty_cache()
-                corpus = dev_mod.Corpus(ctx, lib_mod.KIND_PQ, lib_mod.METRIC_L2, DIM, n)
-                corpus.set_codebook(orc.synth_rows(41, 0, m * KS, DIM // m, 0).reshape(m, KS, DIM // m))
+                corpus = dev_mod.Corpus(ctx, lib_mod.KIND_PQ, lib_mod.METRIC_L2, dim, n)
+                corpus.set_codebook(orc.synth_rows(41, 0, m * KS, dim // m, 0).reshape(m, KS, dim // m))
                 rng = np.random.default_rng(42)
                 for lo in range(0, n, CHUNK):
                     rows = min(CHUNK, n - lo)
@@ -80,7 +84,7 @@ def main():
                                         rng.integers(0, KS, (rows, m), dtype=np.uint8))
                 shape = (n, m)
             c = corpus
-            tq = torch.from_numpy(np.ascontiguousarray(orc.synth_rows(43, 0, nq, DIM, 0))).to(dev)
+            tq = torch.from_numpy(np.ascontiguousarray(orc.synth_rows(43, 0, nq, dim, 0))).to(dev)
             ws_bytes = max(lib.wvg_search_workspace_size(c.handle, j, k) for j in (1, nq))  # `singles` runs on it too
             ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
             oi = torch.empty((nq, k), dtype=torch.int64, device=dev)
@@ -109,7 +113,7 @@ def main():
                                                                        stride, 0, *out))
 
             modes = [device, singles] + ([pipelined] if has_stream else []) + ([pipelined_10pct] if filtered else [])
-            rec = {"lib": os.path.relpath(lib_path, ROOT), "label": args.label, "rows": n, "dim": DIM, "m": m, "ks": KS, "k": k,
+            rec = {"lib": os.path.relpath(lib_path, ROOT), "label": args.label, "rows": n, "dim": dim, "m": m, "cache_reuse": args.cache_reuse, "ks": KS, "k": k,
                    "queries_per_call": nq, "calls_per_run": args.calls, "pq_stream": has_stream,
                    "us_per_call": {fn.__name__: [] for fn in modes}, "median_us": {}}
             if has_stream:

@@ -523,6 +523,33 @@ struct PQShareArgs {
 uint32_t pq_qshare_queries_per_pass(uint32_t m, uint32_t ks, uint32_t k);
 uint32_t pq_qshare_groups(uint64_t ntiles, int num_cus);
 hipError_t launch_scan_pq_qshare(const PQShareArgs &a, uint32_t groups, hipStream_t s);
+// The slice form of that scan (scan_pq_qshare_slice_kernel, wvg_pq_qslice.hip) for codebooks of which
+// not even two LUTs fit LDS (at ks = 256: m >= 96): the same arguments, grid, lists and merge; the
+// image holds S consecutive segments of the pass's 4 LUTs at a time and a wave carries the partial
+// sums of a block of tiles in registers from slice to slice.  4 where a slice of at least 16
+// segments fits, else 1: no shared scan.
+uint32_t pq_qslice_queries_per_pass(uint32_t m, uint32_t ks, uint32_t k);
+hipError_t launch_scan_pq_qslice(const PQShareArgs &a, uint32_t groups, hipStream_t s);
+// Code loads of the two scans: the default cache policy (PLAIN) or non-temporal.  A template argument,
+// not a run-time branch (wvg_bq_qshare.hip: the compiler merges the two arms of such a branch and drops
+// the hint).
+template <bool PLAIN>
+__device__ __forceinline__ uint4 ld_pq_codes(const uint4 *p)
+{
+    if constexpr (PLAIN) {
+        return *p;
+    } else {
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+}
+// Query q's allow word of tile t (PQShareArgs: word t - allow_t0, zero outside the window).
+__device__ __forceinline__ uint64_t pq_qshare_allow(const PQShareArgs &a, uint32_t q, uint64_t t)
+{
+    const uint64_t w = t - a.allow_t0;
+    return w < a.allow_stride ? a.allow[(size_t)q * a.allow_stride + w] : 0ull;
+}
 // Heap replay (wvg_replay.hip).  prefix: per query, thr[q][g] = the k-th smallest
 // distance of ranges 0..g-1's lists (partials [nq][groups][k], ascending; +inf
 // while fewer than k rows precede range g).  filter: each wave's emitted keys

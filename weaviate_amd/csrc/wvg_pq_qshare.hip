@@ -22,27 +22,8 @@ namespace wvg {
 
 typedef float f32x2q __attribute__((ext_vector_type(2)));
 typedef float f32x4q __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4q __attribute__((ext_vector_type(4)));
 
-// Code loads: the default cache policy (PLAIN) or non-temporal.  A template argument, not a run-time
-// branch (wvg_bq_qshare.hip: the compiler merges the two arms of such a branch and drops the hint).
-template <bool PLAIN>
-__device__ __forceinline__ uint4 ld_pq_codes(const uint4 *p)
-{
-    if constexpr (PLAIN) {
-        return *p;
-    } else {
-        const u32x4q v = __builtin_nontemporal_load(reinterpret_cast<const u32x4q *>(p));
-        return make_uint4(v.x, v.y, v.z, v.w);
-    }
-}
-
-// Query j's allow word of tile t (PQShareArgs: word t - allow_t0, zero outside the window).
-__device__ __forceinline__ uint64_t pq_qshare_allow(const PQShareArgs &a, uint32_t q, uint64_t t)
-{
-    const uint64_t w = t - a.allow_t0;
-    return w < a.allow_stride ? a.allow[(size_t)q * a.allow_stride + w] : 0ull;
-}
+// (ld_pq_codes<PLAIN> and pq_qshare_allow: wvg_internal.hpp, shared with the slice form, wvg_pq_qslice.hip)
 
 // ---- the rotated form: m = 32, ks = 256, Q = 4 ----------------------------------------------------
 // K8b's schedule (wvg_pq.hip): lane l (x = l mod 32) reads segment (x + j) mod 32 at step j, so the
@@ -325,8 +306,8 @@ static uint32_t pq_qshare_q_e(uint32_t m, uint32_t ks)
 
 // Queries per pass: the largest of {4, 2} whose image (Q m ks 4 bytes) fits one workgroup's LDS beside the
 // kernel's own static LDS (group_combine_store's buffer, 8 KiB x E), as the code object of the kernel
-// that would be launched states it; 1 = no shared scan (at ks = 256: m >= 96).  A slice-wise image
-// for those is not built.
+// that would be launched states it; 1 = no whole image (at ks = 256: m >= 96; the slice form of the
+// scan, wvg_pq_qslice.hip, serves those in a context that asks for it).
 uint32_t pq_qshare_queries_per_pass(uint32_t m, uint32_t ks, uint32_t k)
 {
     if (m == 0 || ks == 0 || ks > 256 || k == 0 || k > 256) return 1;

@@ -1439,25 +1439,41 @@ static int bq_stream_plain(const wvg_corpus *c, uint64_t tb, uint64_t te)
 // ---- PQ corpora in the pipelined search ----------------------------------------------------------
 // Two or more queries in a context with cache_reuse on, over a codebook whose LUTs fit LDS at least
 // two at a time (pq_qshare_queries_per_pass), take the shared-row PQ scan (scan_pq_qshare_kernel,
-// wvg_pq_qshare.hip) and the list merge: the LUT launch and those two on the caller's stream.  One
-// query, cache_reuse = 0 or a larger codebook is wvg_search_device's route for that nq; with allow
-// lists one launch_scan_pq per query, each with its own window, then one merge.  Results are the
-// (ADC distance, docID)-lexicographic top-k on every route.  A PQ corpus without a codebook has no
-// (m, ks) and hence no route: WVG_ERR_UNSUPPORTED from the three pipelined entry points.
-static bool pq_stream_route(const wvg_corpus *c, uint32_t nq, uint32_t k)
+// wvg_pq_qshare.hip) and the list merge: the LUT launch and those two on the caller's stream.  A
+// larger codebook (at ks = 256: m >= 96) takes the slice form of that scan (scan_pq_qshare_slice_kernel,
+// wvg_pq_qslice.hip, 4 queries per pass) in a context with cache_reuse = 2, the same launches and
+// workspace.  One query, cache_reuse = 0 or a larger codebook under cache_reuse = 1 is
+// wvg_search_device's route for that nq; with allow lists one launch_scan_pq per query, each with its
+// own window, then one merge.  Results are the (ADC distance, docID)-lexicographic top-k on every
+// route.  A PQ corpus without a codebook has no (m, ks) and hence no route: WVG_ERR_UNSUPPORTED from
+// the three pipelined entry points.
+struct PqStreamRoute {
+    uint32_t q = 1;      // queries per pass; 1: no shared scan
+    bool slices = false; // the slice form
+};
+static PqStreamRoute pq_stream_route(const wvg_corpus *c, uint32_t nq, uint32_t k)
 {
-    if (tuning().qshare < 0) return false;
-    return nq >= 2 && c->kind == WVG_KIND_PQ && c->ctx->opt.cache_reuse &&
-           pq_qshare_queries_per_pass(c->pq_m, c->pq_ks, k) >= 2;
+    PqStreamRoute r;
+    if (tuning().qshare < 0 || nq < 2 || c->kind != WVG_KIND_PQ || !c->ctx->opt.cache_reuse) return r;
+    r.q = pq_qshare_queries_per_pass(c->pq_m, c->pq_ks, k);
+    if (r.q < 2 && c->ctx->opt.cache_reuse == 2) {
+        r.q = pq_qslice_queries_per_pass(c->pq_m, c->pq_ks, k);
+        r.slices = r.q >= 2;
+    }
+    return r;
 }
 
-static wvg_stream_plan pq_stream_plan(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k)
+static wvg_stream_plan pq_stream_plan(const wvg_corpus *c, const SearchPlan &p1, uint32_t nq, uint32_t k, bool *slices)
 {
     wvg_stream_plan sp{0u, 1u, p1.empty ? 0u : nq, 0u, 0u};
-    if (p1.empty || !pq_stream_route(c, nq, k)) return sp;
+    *slices = false;
+    if (p1.empty) return sp;
+    const PqStreamRoute r = pq_stream_route(c, nq, k);
+    if (r.q < 2) return sp;
     sp.shared_rows = 1;
-    sp.queries_per_pass = pq_qshare_queries_per_pass(c->pq_m, c->pq_ks, k);
-    sp.passes = (nq + sp.queries_per_pass - 1) / sp.queries_per_pass;
+    sp.queries_per_pass = r.q;
+    sp.passes = (nq + r.q - 1) / r.q;
+    *slices = r.slices;
     return sp;
 }
 
@@ -1500,7 +1516,8 @@ int wvg_search_device_pipelined_plan(wvg_corpus *c, uint32_t nq, uint32_t k, wvg
         return WVG_OK;
     }
     if (c->kind == WVG_KIND_PQ) {
-        *out = pq_stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k);
+        bool slices;
+        *out = pq_stream_plan(c, plan_search(c, 1, k, nullptr, 0), nq, k, &slices);
         return WVG_OK;
     }
     uint32_t seed_tiles;
@@ -1710,7 +1727,8 @@ static int search_pipelined_pq(wvg_corpus *c, const float *d_queries, uint32_t n
             WVG_HIP(launch_fill_empty(d_ids, d_dists, d_counts, nq, k, s));
             return WVG_OK;
         }
-        const wvg_stream_plan sp = pq_stream_plan(c, p, nq, k);
+        bool slices;
+        const wvg_stream_plan sp = pq_stream_plan(c, p, nq, k, &slices);
         if (sp.shared_rows || flt) {
             const uint32_t groups = sp.shared_rows ? pq_qshare_groups(p.te - p.tb, c->ctx->num_cus) : (uint32_t)p.groups;
             const PqStreamLayout l = pq_stream_layout(c, nq, k, groups);
@@ -1745,7 +1763,7 @@ static int search_pipelined_pq(wvg_corpus *c, const float *d_queries, uint32_t n
                 a.metric = c->metric;
                 a.reverse = next_direction(c, sp.passes);  // one direction per pass
                 a.plain = (uint32_t)pq_stream_plain(c, p.tb, p.te);
-                WVG_HIP(launch_scan_pq_qshare(a, groups, s));
+                WVG_HIP(slices ? launch_scan_pq_qslice(a, groups, s) : launch_scan_pq_qshare(a, groups, s));
             } else {  // allow lists without the shared-row scan: K8 takes one window, so one launch per query
                 for (uint32_t i = 0; i < nq; i++) {
                     ScanArgs a = scan_args_for(c, luts + (size_t)i * lpitch, lpitch, 1, k, nullptr, p.tb, p.te);

@@ -105,6 +105,20 @@ typedef struct wvg_options {
                                   Measured with 1024-query batches, k = 10: 12.95 against 23.2 ms at
                                   10M x 768, 4.52 against 5.84 ms at 1M x 1024, 5.40 against 5.67 ms at
                                   1M x 768, but slower at 1M x 512 (3.87 against 3.65 ms).
+                                  4 (opt-in): the bf16 screen for every corpus and every d % 32 == 0, and
+                                  batches at 16 < k <= 256 -- dot, cosine and l2-squared, otherwise the
+                                  conditions of k <= 16 -- take its wide form (K3c-W: survivor pools in
+                                  the workspace instead of 16-key lists; results identical to the exact
+                                  path).  The int8 screens are off in such a context (K3c-W reads the
+                                  bf16 shadow, and a corpus has one shadow); at k <= 16 it behaves as 2
+                                  does for an l2-squared corpus.  k > 256 keeps the select route.  The
+                                  workspace of a wide batch holds the pools, nq * ranges * (2 * max(k,
+                                  64) + 256) * 8 bytes, the range count lowered (never below 8) to keep
+                                  them at 256 MiB; wvg_search_workspace_size is the larger of that and
+                                  the exact route's.  Measured at 10M x 768 with 1024 queries, k = 17 /
+                                  100 / 256: cosine 32.5 / 220 / 297 ms against 124 / 248 / 288 ms,
+                                  l2-squared 45 / 271 / 328 ms against 1017 / 1020 / 1086 ms; 64-query
+                                  batches on a 1M x 128 corpus at k <= 100 are up to 0.3 ms slower.
                                   The first screened search of a corpus allocates its shadow: int8 = dim
                                   + 8 bytes per row of capacity (7.7 GB at 10M x 768; its first build
                                   also takes one pass over the rows for the corpus scale and one host
@@ -331,6 +345,7 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * allocation (caller supplies a workspace of wvg_search_workspace_size bytes,
  * zero-filled once before its first use), so a call can be captured in a
  * hipGraph.  Exception: the first screened batch of a corpus (batch_screen;
+ * under 4 a wide batch, 16 < k <= 256, is a screened batch like any other;
  * dot / cosine / l2-squared) allocates and builds its shadow on `stream`;
  * under capture that never happens -- a corpus without a current shadow takes
  * the exact path, one with a shadow waits for it before the capture (run one

@@ -162,7 +162,8 @@ void shadow_free(wvg_corpus *c);
 // s (built or refreshed there, or waited for).  False: run the exact path.
 bool ensure_shadow(wvg_corpus *c, hipStream_t s);
 // Whether a first build of c's shadow tries the int8 one (K3i; an l2-squared corpus: K3i-L2, only
-// under batch_screen = 3).  No rows, all zeros or an extreme scale still fall back to bf16.
+// under batch_screen = 3; never under batch_screen = 4, whose K3c-W reads the bf16 shadow at every k, so the
+// int8 screens are off in such a context).  No rows, all zeros or an extreme scale still fall back to bf16.
 inline bool shadow_wants_i8(const wvg_corpus *c)
 {
     const int bs = c->ctx->opt.batch_screen;
@@ -176,13 +177,16 @@ inline bool shadow_wants_i8(const wvg_corpus *c)
 struct ScreenWs {
     size_t part = 0, cand = 0, keys = 0, gb = 0, qf = 0, k1 = 0, k2 = 0, em = 0, fl = 0, nf = 0, fbp = 0;
     size_t pids = 0, pd = 0, pc = 0, kb = 0, css = 0, qinv = 0, cq = 0, total = 0;
+    size_t pcnt = 0, qfl = 0;  // K3c-W: per-range kept counts, per-query overflow flags
 };
-ScreenWs screen_ws(uint32_t nq, uint32_t k, uint32_t nrr, uint32_t kbn, uint32_t fb_groups);
+// wide (K3c-W): part holds the survivor pools [nq][nrr][screen_wide_pool(k)]; cand and keys alias it
+ScreenWs screen_ws(uint32_t nq, uint32_t k, uint32_t nrr, uint32_t kbn, uint32_t fb_groups, bool wide = false);
 
 struct SearchPlan {
     uint64_t tb = 0, te = 0;
     int groups = 1;      // scan: workgroups per query; gemm: row ranges (screen: K3c row ranges)
     bool gemm = false;   // K3 batched MFMA path
+    bool wide = false;   // screen: K3c-W (16 < k <= 256, batch_screen = 4), groups its row ranges
     bool screen = false; // the bf16 / int8 screen + exact rescore (gemm: dot / cosine; !gemm: l2-squared, K3c-L2)
     int exact_groups = 1;   // screen: the exact path's groups if the shadow cannot be built (K3b's row ranges;
     bool exact_cosched = false;  // l2-squared has no K3b: the co-scheduled K1 / K1Q plan of the same batch)
@@ -204,7 +208,7 @@ struct SearchPlan {
     }
     size_t workspace_bytes(uint32_t nq, uint32_t k) const
     {
-        if (screen) return std::max(screen_ws(nq, k, (uint32_t)groups, kbn, fb_groups).total, gemm_bytes(nq, k, exact_groups, gemm));
+        if (screen) return std::max(screen_ws(nq, k, (uint32_t)groups, kbn, fb_groups, wide).total, gemm_bytes(nq, k, exact_groups, gemm));
         return gemm_bytes(nq, k, groups, gemm);
     }
 };

@@ -589,6 +589,11 @@ constexpr int SCREEN_M = 16;  // lower bounds kept per (wave, query) and per (ro
 // (K3c-L2 only, which takes any count) has exactly dim / 32, so its shadow is 2 * dim + 4 bytes per row
 inline uint32_t screen_kblocks(uint32_t dim, bool l2 = false) { return l2 ? (dim + 31) / 32 : (dim + 63) / 64 * 2; }
 bool screen_supported(uint32_t dim, int metric, uint32_t k);
+// K3c-W (16 < k <= 256, a batch_screen = 4 context): keys per (row range, query) survivor pool -- room
+// for a compacted pool (2 max(k, 64)) plus what one 256-row block can add -- and its row-range count
+inline uint32_t screen_wide_pool(uint32_t k) { return 2 * (k > 64 ? k : 64) + 256; }
+bool screen_wide_supported(uint32_t dim, int metric, uint32_t k);
+uint32_t screen_wide_ranges(uint32_t nq, uint32_t k, uint64_t ntiles, int num_cus);
 // An upper bound of the L2 norm from the exact square sum in double:
 // rounded up past the float cast; +inf for a non-finite row.
 __device__ __forceinline__ float norm_upper(double ss)
@@ -664,6 +669,11 @@ struct ScreenLaunch {
     uint64_t *cand;        // [nq][nrr * SCREEN_M]
     uint32_t *flist;       // [nq] flagged queries
     uint32_t *nflag;       // count
+    // K3c-W (bf16 shadow only): partials = the pools [nq][nrr][screen_wide_pool(k)], which collect packs
+    // in place into the candidates (cand unused); per (query, range) the kept count and the smallest lower bound the pool let go
+    bool wide = false;
+    uint32_t *pcnt = nullptr;   // [nq][nrr]
+    uint32_t *pdrop = nullptr;  // [nq][nrr] a range's smallest dropped lower bound
     // exact seeds (optional): the rows and distance the final rescore uses
     int metric = 0;
     const float *data = nullptr;  // tiled fp32 rows

@@ -63,6 +63,14 @@ namespace wvg {
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+// The K3i-L2 and K3c-W kernels are compiled without packed fp32 instructions (v_pk_add / mul / fma_f32): the
+// bound's fp32 steps are scalar operations, each rounded as the comment blocks below count them.
+#ifdef __HIP_DEVICE_COMPILE__
+#define WVG_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define WVG_NO_PK_F32
+#endif
+
 constexpr int SC_BQ = 128;                 // queries per workgroup
 constexpr int SC_WAVES = 8;                // 4 (query quarters) x 2 (row halves)
 constexpr int SC_AFR = 8;                  // query fragments per stage (8 groups of 16, one 32-deep K block)
@@ -491,7 +499,7 @@ struct ScreenArgs {
                               // ranges), the others the rest; rsplit[0] = 0: nrr equal ranges
     int cosine;
     uint32_t *gbound;         // [nq] ordered tau; 0xFFFFFFFF = none yet
-    uint64_t *partials;       // [nq][nrr][SCREEN_M]
+    uint64_t *partials;       // [nq][nrr][SCREEN_M] (K3c-W: the survivor pools, [nq][nrr][P])
 };
 
 // Row blocks [b0, b1) of range rr (ScreenArgs::rsplit; the host checks
@@ -760,9 +768,85 @@ __device__ __forceinline__ float sc_u(float s, float e, float h)
     else return s + e;
 }
 
-// The body of K3c (L2 = false: cqp / hg unused) and of K3c-L2.
-template <bool L2>
-__device__ __forceinline__ void screen_body(const ScreenArgs &a, const float *cqp, float hg)
+// K3c-W's compaction of one query's pool (a wave; wave-uniform arguments): the k-th smallest lower
+// bound of its n <= 768 keys tightens the query's bound t, and every key with lower <= t stays (not
+// only k of them: a dropped key at or below the final tau may be a row of the exact top-k), packed
+// at the pool's front.  More than cap such keys (the pool must take another row block): only those
+// below the (cap + 1)-th smallest lower bound x stay, and *drop keeps the minimum of every such x --
+// the smallest lower bound the pool ever let go.  (A later x can be above an earlier one: the fast
+// check admits on u >= sigma, and sigma's rounding slack lets a key slightly above the admission
+// bound in.)  x is no bound of a distance: the caller admits nothing above min(t, *drop) from here
+// on, up to that slack, and collect flags the query if its final tau reaches *drop (K3c's rule for
+// a full list).  Returns (truncated << 63) | (kept << 32) | bits of t.  Out of line, and what it
+// returns is in registers or LDS: the main loop keeps its allocation, nothing goes through a stack.
+constexpr int SW_PMAX = 768;  // 2 * max(k, 64) + 256 at k = 256: 12 keys per lane
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+__device__ __attribute__((noinline)) uint64_t sc_compact(uint64_t *pool, uint32_t n, uint32_t K, uint32_t cap,
+                                                         float emax, int cosine, float t, lds_u32 *drop)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    uint64_t key[SW_PMAX / 64];
+#pragma unroll
+    for (int i = 0; i < SW_PMAX / 64; i++) {
+        const uint32_t j = 64u * i + lane;
+        key[i] = j < n ? pool[j] : WVG_KEY_NONE;
+    }
+    // the R-th smallest ordered lower bound (R <= n) = the largest v with fewer than R values below it, bit by bit
+    auto rth = [&](uint32_t R) {
+        uint32_t v = 0;
+        for (int bit = 31; bit >= 0; bit--) {
+            const uint32_t c = v | (1u << bit);
+            int below = 0;
+#pragma unroll
+            for (int i = 0; i < SW_PMAX / 64; i++) below += (uint32_t)(key[i] >> 32) < c;
+            for (int off = 32; off > 0; off >>= 1) below += __shfl_xor(below, off);
+            if ((uint32_t)below < R) v = c;
+        }
+        return v;
+    };
+    if (n >= K) t = fminf(t, sc_tau_k(wvg_unord_f32(rth(K)), emax, cosine));
+    uint32_t within = 0;
+#pragma unroll
+    for (int i = 0; i < SW_PMAX / 64; i++)
+        within += (uint32_t)__popcll(__ballot(key[i] != WVG_KEY_NONE && key_lower(key[i]) <= t));
+    const bool trunc = within > cap;
+    uint32_t x = 0xFFFFFFFFu;
+    if (trunc) {
+        x = rth(cap + 1);
+        if (lane == 0) *drop = min((uint32_t)*drop, x);
+    }
+    uint32_t kept = 0;
+#pragma unroll
+    for (int i = 0; i < SW_PMAX / 64; i++) {
+        const bool keep = key[i] != WVG_KEY_NONE && (trunc ? (uint32_t)(key[i] >> 32) < x : key_lower(key[i]) <= t);
+        const uint64_t bal = __ballot(keep);
+        if (keep) pool[kept + __popcll(bal & ((1ull << lane) - 1ull))] = key[i];
+        kept += (uint32_t)__popcll(bal);
+    }
+    return ((uint64_t)trunc << 63) | ((uint64_t)kept << 32) | __float_as_uint(t);
+}
+
+// The body of K3c (L2 = false: cqp / hg unused), of K3c-L2, and (WIDE) of K3c-W, 16 < k <= 256.
+//
+// K3c-W.  The main loop, the bound and the fast check are K3c's; what differs is where a survivor
+// goes.  A list of k keys per (wave, query) does not fit LDS beyond k = 16, so a (row range, query)
+// owns a pool of P = 2 max(k, 64) + 256 keys in HBM (it stays in L2) and LDS holds only the pool's
+// fill count, shared by the two waves that score the query's two row halves.  A survivor claims a
+// position with one LDS atomic and stores its key: per lane, no wave-serial insertion.  A row block
+// adds at most 256 keys to a pool, so a count that is at most P - 256 at every block boundary never
+// passes P.  A lane that pushes a count past P - 256 raises the block's flag word (two words, by
+// block parity: a wave may be one block ahead of the slowest reader); after the block's barrier
+// every wave reads it, so the whole workgroup compacts or none does.  A compaction (sc_compact)
+// selects the pool's k-th lower bound, tightens tau_q and both waves' thresholds and keeps every
+// key at or below tau_q -- or, when more than P - 256 are, the P - 256 smallest, remembering the
+// smallest lower bound it let go (wdrop; the thresholds then admit nothing above it).  The range's
+// last compaction writes the kept count and that bound and publishes tau_q (atomicMin on gbound);
+// collect flags a query whose final tau reaches a range's dropped bound (mass ties, a range with
+// more than P - 256 rows inside the final bound) for the shared K1 rescan: no result depends on P.
+// (wP, wpcnt, wpdrop: K3c-W's pool size and, per (query, range), the kept count and the dropped bound)
+template <bool L2, bool WIDE = false>
+__device__ __forceinline__ void screen_body(const ScreenArgs &a, const float *cqp, float hg, uint32_t wP = 0,
+                                            uint32_t *wpcnt = nullptr, uint32_t *wpdrop = nullptr)
 {
 #ifdef WVG_TOOLS
     uint32_t n_blk = 0, n_slow = 0, n_call = 0;
@@ -792,7 +876,16 @@ __device__ __forceinline__ void screen_body(const ScreenArgs &a, const float *cq
     // per-query constants and thresholds
     sc_copy_consts<false>(a, q0, SC_WAVES * 64, ck1, ck2, cem, nullptr, nullptr);
     sc_init_thresholds<32, 4, SC_WAVES>(a, q0, tid, cosine, tau, sig);  // 4 query quarters x 2 row halves
-    for (int i = tid; i < SC_WAVES * 32 * M; i += SC_WAVES * 64) lists[i] = WVG_KEY_NONE;
+    // (K3c-W: the list region holds the pools' fill counts [128], the two compaction flag words, the
+    // dropped bounds [128] and the queries' valid bounds tau_q [128] -- tau[] is what a wave admits)
+    uint32_t *wcnt = reinterpret_cast<uint32_t *>(lists), *wflag = wcnt + SC_BQ, *wdrop = wflag + 4;
+    float *wtau = reinterpret_cast<float *>(wdrop + SC_BQ);
+    if constexpr (WIDE) {
+        for (int i = tid; i < SC_BQ + 4; i += SC_WAVES * 64) wcnt[i] = 0;
+        for (int i = tid; i < SC_BQ; i += SC_WAVES * 64) wdrop[i] = 0xFFFFFFFFu;
+    } else {
+        for (int i = tid; i < SC_WAVES * 32 * M; i += SC_WAVES * 64) lists[i] = WVG_KEY_NONE;
+    }
     if constexpr (L2) {
         for (int i = tid; i < SC_BQ; i += SC_WAVES * 64) ccq[i] = cqp[q0 + (uint32_t)i];
         __syncthreads();  // tau is in place: its u-space form with the query's Cq (slot (w, ql) = query 32 (w & 3) + ql)
@@ -802,6 +895,54 @@ __device__ __forceinline__ void screen_body(const ScreenArgs &a, const float *cq
         }
     }
     __syncthreads();
+    // K3c-W: every wave of the workgroup enters; wave w compacts the pools of queries w, w + 8, ...
+    // that passed P - 256 (last: every pool, whose kept count and tau are the range's output)
+    if constexpr (WIDE) {
+        for (int i = tid; i < SC_BQ; i += SC_WAVES * 64) wtau[i] = tau[i];  // (row half 0's slots: query i)
+        __syncthreads();
+    }
+    auto compact_pools = [&](bool last, uint32_t flagword) {
+        if constexpr (WIDE) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pools' stores
+            __threadfence_block();
+            __syncthreads();
+            const uint32_t P = wP;
+            for (int qw = w; qw < SC_BQ; qw += SC_WAVES) {
+                const uint32_t q = q0 + (uint32_t)qw;
+                if (q >= a.nq) break;
+                const uint32_t raw = wcnt[qw];
+                if (!last && raw <= P - 256) continue;
+                const int sl = (qw >> 5) * 32 + (qw & 31);  // the query's slot of row half 0 (half 1: + 4 * 32)
+                float t = wtau[qw];
+                uint32_t kept = 0;
+                if (raw > 0) {
+                    const uint64_t r = sc_compact(a.partials + ((size_t)q * a.nrr + rr) * P, min(raw, P), (uint32_t)K,
+                                                  P - 256, cem[qw], cosine, t, (lds_u32 *)(wdrop + qw));
+                    kept = (uint32_t)(r >> 32) & 0x7FFFFFFFu;
+                    t = __uint_as_float((uint32_t)r);
+                }
+                if (lane == 0) {
+                    if (raw > P) wdrop[qw] = 0;  // keys lost past the pool (never, by the block rule): always flagged
+                    const uint32_t dr = wdrop[qw];
+                    const float wt = dr == 0xFFFFFFFFu ? t : fminf(t, wvg_unord_f32(dr));  // (ord 0: NaN, fminf keeps t)
+                    const float sg = L2 ? sc_sigma_l2(wt, ccq[qw]) : sc_sigma(wt, cosine);
+                    wcnt[qw] = kept;
+                    wtau[qw] = t;
+                    tau[sl] = tau[sl + 4 * 32] = wt;
+                    sig[sl] = sig[sl + 4 * 32] = sg;
+                    if (last) {
+                        wpcnt[(size_t)q * a.nrr + rr] = kept;
+                        wpdrop[(size_t)q * a.nrr + rr] = dr;
+                        if (t < __builtin_inff()) atomicMin(a.gbound + q, wvg_ord_f32(t));
+                    }
+                }
+            }
+            if (tid == 0) wflag[flagword] = 0;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __threadfence_block();
+            __syncthreads();
+        }
+    };
     if (blk0 >= blk1) goto publish;
     {
         // stage loader: wave w moves fragments 3w .. 3w+2 of a stage (A 0..7, B 8..23);
@@ -1031,6 +1172,21 @@ __device__ __forceinline__ void screen_body(const ScreenArgs &a, const float *cq
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
                             const float u = sc_u<L2>(acc[mq][nr][r], __builtin_fmaf(nrm[nr], k1r[mq][r], k2r[mq][r]), hx[nr]);
+                            if constexpr (WIDE) {
+                                // K3c-W: each surviving lane claims a pool position of its own query
+                                const int qw = 32 * wq + 16 * mq + qlane + r;
+                                if (!(u < svr[mq][r]) && ((m16 >> (lane & 15)) & 1ull) && q0 + (uint32_t)qw < a.nq) {
+                                    const float lower = L2 ? sc_lower_l2(u, ccq[qw]) : sc_lower(u, cosine);
+                                    const uint32_t slot = (uint32_t)((a.tile_begin + blk * 4) * 64 + 128 * wr + 16 * nr +
+                                                                     (lane & 15));
+                                    const uint32_t pos = atomicAdd(&wcnt[qw], 1u);
+                                    if (pos < wP)
+                                        a.partials[((size_t)(q0 + (uint32_t)qw) * a.nrr + rr) * wP + pos] =
+                                            ((uint64_t)wvg_ord_f32(lower) << 32) | slot;
+                                    if (pos + 256 >= wP) wflag[blk & 1] = 1u;
+                                }
+                                continue;
+                            }
                             uint64_t pass = __ballot(!(u < svr[mq][r])) & m64 & qlive[mq][r];
                             while (pass) {  // rare after the first row blocks of a range
                                 const int src = __builtin_ctzll(pass);
@@ -1069,6 +1225,20 @@ __device__ __forceinline__ void screen_body(const ScreenArgs &a, const float *cq
             // unit u + 1 landed (its loads are the oldest in flight), then everyone's
             wait_stages(u + 3 < U ? 2 : (u + 2 < U ? 1 : 0));
             raw_barrier();
+            if constexpr (WIDE) {
+                // a row block ended and every wave is past its epilogue: did a pool pass P - 256?
+                // (asm, as the epilogue's reads: the word is in no DMA buffer)
+                if (ks == 0) {
+                    const uint32_t fw = (uint32_t)(blk - 1) & 1u;
+                    uint32_t f;
+                    asm volatile("ds_read_b32 %0, %1\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=v"(f)
+                                 : "v"((uint32_t)(uintptr_t)(wflag + fw))
+                                 : "memory");
+                    if (__builtin_amdgcn_readfirstlane((int)f)) compact_pools(false, fw);
+                }
+            }
         }
     }
 publish:
@@ -1081,6 +1251,10 @@ publish:
     }
 #endif
     __syncthreads();
+    if constexpr (WIDE) {
+        compact_pools(true, 0);  // the range's output: every pool's kept keys, their count, tau_q
+        return;
+    }
     // merge the two row halves' lists per query (waves wq and wq + 4), by rank:
     // wave w takes queries w, w + 8, ... of the workgroup
     for (int qw = w; qw < SC_BQ; qw += SC_WAVES) {
@@ -1108,6 +1282,24 @@ __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_kernel(ScreenArgs a) 
 __global__ __launch_bounds__(SC_WAVES * 64, 1) void screen_l2_kernel(ScreenL2Args a)
 {
     screen_body<true>(a.s, a.cq, a.hg);
+}
+
+// K3c-W (16 < k <= 256; "K3c-W" above), dot / cosine and l2-squared
+struct ScreenWideArgs {
+    ScreenL2Args l;   // K3c's / K3c-L2's arguments (dot / cosine: cq, hg unused); s.partials = the pools [nq][nrr][P]
+    uint32_t P;       // keys per pool (screen_wide_pool)
+    uint32_t *pcnt;   // [nq][nrr] keys a finished range kept
+    uint32_t *pdrop;  // [nq][nrr] the smallest (ordered) lower bound a range's pool let go; 0xFFFFFFFF: none
+};
+
+__global__ WVG_NO_PK_F32 __launch_bounds__(SC_WAVES * 64, 1) void screen_wide_kernel(ScreenWideArgs a)
+{
+    screen_body<false, true>(a.l.s, nullptr, 0.f, a.P, a.pcnt, a.pdrop);
+}
+
+__global__ WVG_NO_PK_F32 __launch_bounds__(SC_WAVES * 64, 1) void screen_wide_l2_kernel(ScreenWideArgs a)
+{
+    screen_body<true, true>(a.l.s, a.l.cq, a.l.hg, a.P, a.pcnt, a.pdrop);
 }
 
 // ---------------------------------------------------------------------------
@@ -2323,13 +2515,7 @@ constexpr int SJ_LDS_L2 = SJ_LDS + SD_BQ * 4;  // + the workgroup's Cq
 constexpr int si_lds_l2(int nb) { return si_lds(nb) + SD_BQ * 4; }
 static_assert(SJ_LDS_L2 <= 160 * 1024 && si_lds_l2(8) <= 160 * 1024, "K3i-L2's LDS");
 
-// The K3i-L2 kernels are compiled without packed fp32 instructions (v_pk_add / mul / fma_f32): the bound's
-// fp32 steps are scalar operations, each rounded as the comment block above counts them.
-#ifdef __HIP_DEVICE_COMPILE__
-#define WVG_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define WVG_NO_PK_F32
-#endif
+// (The K3i-L2 kernels are compiled without packed fp32 instructions: WVG_NO_PK_F32, above.)
 
 template <int KBN>
 __global__ WVG_NO_PK_F32 __launch_bounds__(SD_WAVES * 64, 1) void screen_i8_l2_kernel(ScreenL2I8Args a)
@@ -3078,6 +3264,97 @@ __global__ __launch_bounds__(256) void screen_collect_kernel(const uint64_t *par
     if (threadIdx.x == 0 && ovf) flist[atomicAdd(nflag, 1u)] = q;
 }
 
+// K3c-W's collect, per query.  The union of the ranges' kept keys -- pcnt[rr] keys at the front of
+// pool rr, any number of them -- stays in HBM: tau* = the k-th smallest lower of the union + 2 Emax
+// by a 4-pass radix select that streams the union once per pass; the keys with lower <= min(tau*,
+// gbound) are then packed at the front of the query's [nrr * P] pool region in place (a chunk's 256
+// reads finish before its writes start, and a write position never passes the keys read so far), the
+// rest KEY_NONE: the rescore and the merge take that region as their candidate row.  A query with a
+// pool let go of a key at or below that bound (pdrop) keeps no candidate and joins the rescan list.
+__global__ __launch_bounds__(256) void screen_collect_wide_kernel(uint64_t *pools, const uint32_t *pcnt,
+                                                                  const uint32_t *pdrop, uint32_t nrr, uint32_t P,
+                                                                  uint32_t k, const float *emax, int cosine,
+                                                                  uint32_t *flist, uint32_t *nflag,
+                                                                  const uint32_t *gbound)
+{
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh_prefix, sh_need, sh_total;
+    const uint32_t q = blockIdx.x, lane = threadIdx.x & 63;
+    uint64_t *reg = pools + (size_t)q * nrr * P;
+    const uint32_t *cnt = pcnt + (size_t)q * nrr;
+    const size_t n_all = (size_t)nrr * P;
+    __shared__ int ovf;
+    if (threadIdx.x == 0) {
+        ovf = 0;
+        sh_total = 0;
+        sh_prefix = 0;
+        sh_need = k;
+    }
+    __syncthreads();
+    uint32_t mine = 0;
+    for (uint32_t rr = threadIdx.x; rr < nrr; rr += 256) mine += min(cnt[rr], P);
+    if (mine) atomicAdd(&sh_total, mine);
+    __syncthreads();
+    float t = __builtin_inff();
+    if (sh_total >= k) {
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[threadIdx.x] = 0;
+            __syncthreads();
+            const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+            const uint32_t pre = sh_prefix;
+            for (uint32_t rr = 0; rr < nrr; rr++) {
+                const uint32_t c = min(cnt[rr], P);
+                for (uint32_t i = threadIdx.x; i < c; i += 256) {
+                    const uint32_t v = (uint32_t)(reg[(size_t)rr * P + i] >> 32);
+                    if ((v & hi_mask) == (pre & hi_mask)) atomicAdd(&hist[(v >> shift) & 255u], 1u);
+                }
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                uint32_t need = sh_need, cum = 0, dg = 255;
+                for (uint32_t d = 0; d < 256; d++) {
+                    if (cum + hist[d] >= need) {
+                        dg = d;
+                        break;
+                    }
+                    cum += hist[d];
+                }
+                sh_need = need - cum;
+                sh_prefix = pre | (dg << shift);
+            }
+            __syncthreads();
+        }
+        t = sc_tau_k(wvg_unord_f32(sh_prefix), emax[q], cosine);
+    }
+    const uint32_t gb = gbound[q];
+    if (gb != 0xFFFFFFFFu) t = fminf(t, wvg_unord_f32(gb));
+    for (uint32_t rr = threadIdx.x; rr < nrr; rr += 256)
+        if (pdrop[(size_t)q * nrr + rr] <= wvg_ord_f32(t)) ovf = 1;  // a dropped key may be a row of the top-k
+    __syncthreads();
+    if (ovf) {
+        for (size_t i = threadIdx.x; i < n_all; i += 256) reg[i] = WVG_KEY_NONE;
+        if (threadIdx.x == 0) flist[atomicAdd(nflag, 1u)] = q;
+        return;
+    }
+    if (threadIdx.x == 0) sh_total = 0;
+    __syncthreads();
+    for (uint32_t rr = 0; rr < nrr; rr++) {
+        const uint32_t c = min(cnt[rr], P);
+        for (uint32_t i0 = 0; i0 < c; i0 += 256) {
+            const uint32_t i = i0 + threadIdx.x;
+            const uint64_t e = i < c ? reg[(size_t)rr * P + i] : WVG_KEY_NONE;
+            const bool keep = e != WVG_KEY_NONE && key_lower(e) <= t;
+            __syncthreads();  // the chunk is read
+            const uint64_t bal = __ballot(keep);
+            uint32_t base = 0;
+            if (lane == 0 && bal) base = atomicAdd(&sh_total, (uint32_t)__popcll(bal));
+            base = __shfl(base, 0);
+            if (keep) reg[base + __popcll(bal & ((1ull << lane) - 1ull))] = e;
+        }
+    }
+    __syncthreads();
+    for (size_t i = (size_t)sh_total + threadIdx.x; i < n_all; i += 256) reg[i] = WVG_KEY_NONE;
+}
 
 __global__ __launch_bounds__(256) void screen_fill_kernel(uint32_t *p, uint32_t n, uint32_t v)
 {
@@ -3108,6 +3385,32 @@ bool screen_supported(uint32_t dim, int metric, uint32_t k)
 {
     return dim % 32 == 0 && dim > 0 && k > 0 && k <= (uint32_t)SCREEN_M &&
            (metric == WVG_M_DOT || metric == WVG_M_COSINE || metric == WVG_M_L2);
+}
+
+// Whether K3c-W applies (a batch_screen = 4 context): the bf16 shadow's dims, k past the lists and
+// within the pools (SW_PMAX keys, 12 per lane of a compacting wave).
+bool screen_wide_supported(uint32_t dim, int metric, uint32_t k)
+{
+    return dim % 32 == 0 && dim > 0 && k > (uint32_t)SCREEN_M && k <= 256 && screen_wide_pool(k) <= (uint32_t)SW_PMAX &&
+           (metric == WVG_M_DOT || metric == WVG_M_COSINE || metric == WVG_M_L2);
+}
+
+// K3c-W's row ranges: K3c's count, capped so that the pools -- nq * nrr * P keys, the workspace's
+// one large part (candidates and rescored keys reuse them in place) -- stay within 256 MiB, then
+// down to whole rounds of workgroups (one per CU) where more than one round is left.
+uint32_t screen_wide_ranges(uint32_t nq, uint32_t k, uint64_t ntiles, int num_cus)
+{
+    const uint64_t nqb = (nq + SC_BQ - 1) / SC_BQ, nblk = (ntiles + 3) / 4;
+    uint64_t want = screen_row_ranges(nq, ntiles, num_cus);
+    const uint64_t cap = (256ull << 20) / ((uint64_t)nq * screen_wide_pool(k) * 8);
+    if (want > cap) {
+        want = std::max<uint64_t>(8, cap / 8 * 8);
+        if (num_cus > 0) {
+            const uint64_t step = std::lcm<uint64_t>(8, (uint64_t)num_cus / std::gcd<uint64_t>((uint64_t)num_cus, nqb));
+            if (want >= step) want = want / step * step;
+        }
+    }
+    return (uint32_t)std::max<uint64_t>(1, std::min(want, nblk));
 }
 
 #ifdef WVG_TOOLS
@@ -3222,13 +3525,15 @@ static const ScreenKernel *pick_screen_kernel(bool i8, uint32_t kbn, int variant
 hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
 {
     const bool i8 = L.i8 && screen_i8_supported(L.dim);  // (l2-squared: only under batch_screen = 3, K3i-L2)
+    if (L.wide && (L.i8 || !L.pcnt || !L.pdrop || screen_wide_pool(L.k) > (uint32_t)SW_PMAX)) return hipErrorInvalidValue;
     const uint32_t kbn = i8 ? L.dim / 64 : screen_kblocks(L.dim, L.l2);  // (K3i: 64-deep int8 K blocks)
     const bool l2c = L.l2 && !i8;  // K3c-L2 (the bf16 shadow)
     const uint32_t nq_pad = (L.nq + SC_BQ - 1) / SC_BQ * SC_BQ, nqb = nq_pad / SC_BQ;
     hipError_t e;
     // the kernel first: an unsupported (variant, diag) starts nothing
     // (l2-squared: K3c-L2 or K3i-L2 whatever the variant; a diagnostic has no L2 form)
-    const ScreenKernel *sk = l2c    ? pick_screen_kernel(false, kbn, 1, 0)
+    // (K3c-W: K3c's geometry and LDS, its own two kernels)
+    const ScreenKernel *sk = l2c || L.wide ? pick_screen_kernel(false, kbn, 1, 0)
                              : L.l2 ? pick_screen_kernel(true, kbn, 0, 0, true)
                                     : pick_screen_kernel(i8, kbn, tuning().screen_variant, tuning().screen_diag);
     if (!sk || (L.l2 && (tuning().screen_diag != 0 || !L.cq))) return hipErrorInvalidValue;
@@ -3240,6 +3545,14 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
                                 hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_L2) == hipSuccess;
         (void)attr_l2;
     }
+    if (L.wide) {
+        static const bool attr_w =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_wide_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS) == hipSuccess &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&screen_wide_l2_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_L2) == hipSuccess;
+        (void)attr_w;
+    }
     // one launch of the chosen kernel over the ranges in x (K3c-L2 and K3i-L2 wrap x with Cq and hg)
     const float hg = L.l2 ? screen_l2_hg(L.dim) : 0.f;
     auto launch = [&](const ScreenArgs &x, uint32_t blocks, hipEvent_t e0, hipEvent_t e1) {
@@ -3249,6 +3562,16 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
                 hipExtLaunchKernelGGL(sk->fn_l2, dim3(blocks), dim3(threads), lds, s, e0, e1, 0u, xl);
             else
                 hipLaunchKernelGGL(sk->fn_l2, dim3(blocks), dim3(threads), lds, s, xl);
+        } else if (L.wide) {
+            const ScreenWideArgs xl{{x, L.cq, hg}, screen_wide_pool(L.k), L.pcnt, L.pdrop};
+            if (L.l2 && (e0 || e1))
+                hipExtLaunchKernelGGL(screen_wide_l2_kernel, dim3(blocks), dim3(threads), lds, s, e0, e1, 0u, xl);
+            else if (L.l2)
+                hipLaunchKernelGGL(screen_wide_l2_kernel, dim3(blocks), dim3(threads), lds, s, xl);
+            else if (e0 || e1)
+                hipExtLaunchKernelGGL(screen_wide_kernel, dim3(blocks), dim3(threads), lds, s, e0, e1, 0u, xl);
+            else
+                hipLaunchKernelGGL(screen_wide_kernel, dim3(blocks), dim3(threads), lds, s, xl);
         } else if (L.l2) {
             const ScreenL2Args xl{x, L.cq, hg};
             if (e0 || e1)
@@ -3294,6 +3617,7 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
     // (kernels, not memsets, reset the bounds and the flag count: a captured device search replays
     // them in order with the launches around them)
     hipLaunchKernelGGL(screen_fill_kernel, dim3((L.nq + 255) / 256), dim3(256), 0, s, L.gbound, L.nq, 0xFFFFFFFFu);
+    // (K3c-W's pools, counts and dropped bounds need none: every range writes its own, collect reads no key past a count)
     if ((e = hipGetLastError()) != hipSuccess) return e;
     // profiling: one event pair spans every phase and the seeds between them (taken
     // before the pilot, whose K3b launch would otherwise bind them)
@@ -3309,7 +3633,9 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
     const uint64_t sp_tiles = std::min<uint64_t>((uint64_t)std::max(tuning().screen_pilot_screen, 0),
                                                  L.tile_end - L.tile_begin);
     uint32_t sp_rr = 0;
-    if (sp_tiles > 0 && L.pilot_part && L.data && L.pilot_part_lists > 0) {
+    // (K3c-W: the screen pilot's scratch and exact seed are built on SCREEN_M-key lists; its pilot is K3b / K1,
+    // whose exact k-th distance over their rows holds for any k they can run)
+    if (!L.wide && sp_tiles > 0 && L.pilot_part && L.data && L.pilot_part_lists > 0) {
         const uint64_t nb = (sp_tiles + 3) / 4;
         uint64_t want = std::min<uint64_t>(((uint64_t)L.num_cus / nqb + 7) / 8 * 8, nb);
         want = std::min<uint64_t>(want, (uint64_t)L.pilot_part_lists * L.k / SCREEN_M);  // the scratch's capacity
@@ -3462,7 +3788,7 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
         const hipEvent_t e0 = ph == 0 ? ev.start : nullptr, e1 = ph + 1 == nph ? ev.stop : nullptr;
         launch(a, nqb * a.nrr_l, e0, e1);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (ph + 1 < nph) {
+        if (ph + 1 < nph && !L.wide) {  // (K3c-W: a later phase starts from the finished ranges' published taus)
             if (seed_exact) {
                 if ((e = exact_seed(bounds[ph + 1])) != hipSuccess) return e;
             } else {
@@ -3477,6 +3803,11 @@ hipError_t launch_screen(const ScreenLaunch &L, hipStream_t s)
     // the final candidates: lower <= min(tau*, gbound); with the exact seed over every
     // range, gbound ~ the k-th exact distance, about one Emax below tau* -- a third of
     // the rows to rescore on 10M x 768 cosine
+    if (L.wide) {
+        hipLaunchKernelGGL(screen_collect_wide_kernel, dim3(L.nq), dim3(256), 0, s, L.partials, L.pcnt, L.pdrop, L.nrr,
+                           screen_wide_pool(L.k), L.k, L.emax, L.cosine, L.flist, L.nflag, L.gbound);
+        return hipGetLastError();
+    }
     if (seed_final && (e = exact_seed(L.nrr)) != hipSuccess) return e;
     hipLaunchKernelGGL(screen_collect_kernel, dim3(L.nq), dim3(256), 0, s, L.partials, L.nrr, L.nrr, L.k, L.emax,
                        L.cosine, L.cand, L.flist, L.nflag, L.gbound);

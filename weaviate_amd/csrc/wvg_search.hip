@@ -185,14 +185,15 @@ static uint32_t k1_cache_tail(const wvg_corpus *c, uint64_t tb, uint64_t te)
     return (uint32_t)std::max<uint64_t>(1, (256ull * K1_CACHE_BYTES) / bytes);
 }
 
-ScreenWs screen_ws(uint32_t nq, uint32_t k, uint32_t nrr, uint32_t kbn, uint32_t fb_groups)
+ScreenWs screen_ws(uint32_t nq, uint32_t k, uint32_t nrr, uint32_t kbn, uint32_t fb_groups, bool wide)
 {
     ScreenWs w;
     Carver cv;
-    const size_t nq_pad = (size_t)(nq + 127) / 128 * 128, ncand = (size_t)nrr * SCREEN_M;
+    const size_t nq_pad = (size_t)(nq + 127) / 128 * 128, ncand = (size_t)nrr * (wide ? screen_wide_pool(k) : SCREEN_M);
     w.part = cv.take(nq * ncand * 8);
-    w.cand = cv.take(nq * ncand * 8);
-    w.keys = cv.take(nq * ncand * 8);
+    // (K3c-W: the pools are packed into the candidates and rescored in place)
+    w.cand = wide ? w.part : cv.take(nq * ncand * 8);
+    w.keys = wide ? w.part : cv.take(nq * ncand * 8);
     w.gb = cv.take((size_t)nq * 4);
     w.qf = cv.take(nq_pad / 16 * kbn * 1024);
     w.k1 = cv.take(nq_pad * 4);
@@ -208,6 +209,10 @@ ScreenWs screen_ws(uint32_t nq, uint32_t k, uint32_t nrr, uint32_t kbn, uint32_t
     w.css = cv.take(nq_pad * 4);
     w.qinv = cv.take(nq_pad * 4);
     w.cq = cv.take(nq_pad * 4);  // K3c-L2's
+    if (wide) {
+        w.pcnt = cv.take((size_t)nq * nrr * 4);
+        w.qfl = cv.take((size_t)nq * nrr * 4);
+    }
     w.total = cv.off;
     return w;
 }
@@ -236,14 +241,23 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
     if (c->kind == WVG_KIND_BQ && nq == 1 && tuning().groups_per_cu <= 0)  // (each wave >= 2 tiles)
         p.groups = (int)std::min<uint64_t>(3ull * (uint64_t)c->ctx->num_cus, std::max<uint64_t>(1, (p.te - p.tb) / 8));
     // bf16 screen + exact rescore for the batches it applies to (results identical to K3b)
-    if (p.gemm && c->ctx->opt.batch_screen && screen_supported(c->dim, c->metric, k) && c->dim % 4 == 0 &&
-        !c->sh_failed) {
-        p.screen = true;
-        p.exact_groups = p.groups;
-        p.groups = (int)screen_row_ranges(nq, std::max<uint64_t>(1, p.te - p.tb), c->ctx->num_cus);
+    // (batch_screen = 4: K3c-W takes the same batches at 16 < k <= 256)
+    const bool wide = c->ctx->opt.batch_screen == 4 && screen_wide_supported(c->dim, c->metric, k);
+    const uint64_t ntiles = std::max<uint64_t>(1, p.te - p.tb);
+    // the flagged queries' K1 rescan: its partial lists are [nq][fb_groups][k], so the wide k take fewer groups
+    auto fb_groups = [&]() {
         ScanArgs a1 = a;
         a1.nq = 1;
-        p.fb_groups = (uint32_t)std::min(scan_groups_for(a1, c->ctx->num_cus), c->ctx->num_cus);
+        return (uint32_t)std::min(scan_groups_for(a1, c->ctx->num_cus), wide ? 32 : c->ctx->num_cus);
+    };
+    if (p.gemm && c->ctx->opt.batch_screen && (screen_supported(c->dim, c->metric, k) || wide) && c->dim % 4 == 0 &&
+        !c->sh_failed) {
+        p.screen = true;
+        p.wide = wide;
+        p.exact_groups = p.groups;
+        p.groups = wide ? (int)screen_wide_ranges(nq, k, ntiles, c->ctx->num_cus)
+                        : (int)screen_row_ranges(nq, ntiles, c->ctx->num_cus);
+        p.fb_groups = fb_groups();
         p.kbn = screen_kblocks(c->dim);
     }
     // PQ batches: the nq queries of one row range run side by side on one XCD and share its L2
@@ -274,18 +288,18 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
     // the same shape would take K3c (a batch: nq >= 2).  There is no K3b for l2-squared, so the plan
     // above -- the co-scheduled K1 / K1Q -- stays as the path of a shadow that cannot be used.
     if (gemm_ok && c->kind == WVG_KIND_F32 && c->metric == WVG_METRIC_L2 && mn > 0 && nq >= mn && nq >= 2 &&
-        !c->ctx->order512 && c->ctx->opt.batch_screen && screen_supported(c->dim, c->metric, k) && c->dim % 4 == 0 &&
-        !c->sh_failed) {
+        !c->ctx->order512 && c->ctx->opt.batch_screen && (screen_supported(c->dim, c->metric, k) || wide) &&
+        c->dim % 4 == 0 && !c->sh_failed) {
         p.screen = true;
+        p.wide = wide;
         p.exact_groups = p.groups;
         p.exact_cosched = p.cosched;
         p.exact_mq = p.mq;
         p.cosched = false;
         p.mq = 0;
-        p.groups = (int)screen_row_ranges(nq, std::max<uint64_t>(1, p.te - p.tb), c->ctx->num_cus);
-        ScanArgs a1 = a;
-        a1.nq = 1;
-        p.fb_groups = (uint32_t)std::min(scan_groups_for(a1, c->ctx->num_cus), c->ctx->num_cus);
+        p.groups = wide ? (int)screen_wide_ranges(nq, k, ntiles, c->ctx->num_cus)
+                        : (int)screen_row_ranges(nq, ntiles, c->ctx->num_cus);
+        p.fb_groups = fb_groups();
         // (K3i-L2's int8 fragments take dim / 64 blocks of the same size; the workspace keeps the bf16
         // count, as a dot corpus's does: a plan made before the shadow exists must hold the bf16 fallback)
         p.kbn = screen_kblocks(c->dim, true);
@@ -298,8 +312,9 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
 static int run_screen(wvg_corpus *c, const ScanArgs &a, const SearchPlan &p, char *ws, uint64_t *ids, float *dists,
                       uint32_t *counts, hipStream_t s)
 {
-    const uint32_t nq = a.nq, k = a.k, nrr = (uint32_t)p.groups, ncand = nrr * SCREEN_M;
-    const ScreenWs w = screen_ws(nq, k, nrr, p.kbn, p.fb_groups);
+    const uint32_t nq = a.nq, k = a.k, nrr = (uint32_t)p.groups;
+    const uint32_t ncand = nrr * (p.wide ? screen_wide_pool(k) : (uint32_t)SCREEN_M);
+    const ScreenWs w = screen_ws(nq, k, nrr, p.kbn, p.fb_groups, p.wide);
     ScreenLaunch L{};
     L.shadow = c->d_shadow;
     L.norms = c->d_norms;
@@ -341,6 +356,15 @@ static int run_screen(wvg_corpus *c, const ScanArgs &a, const SearchPlan &p, cha
     L.qinv = (float *)(ws + w.qinv);
     L.l2 = c->metric == WVG_METRIC_L2;
     L.cq = (float *)(ws + w.cq);
+    L.wide = p.wide;
+    if (p.wide) {
+        L.pcnt = (uint32_t *)(ws + w.pcnt);
+        L.pdrop = (uint32_t *)(ws + w.qfl);
+        // the pilot's partial lists go into the pools, free until the first range starts: the rescan's lists
+        // (fb_groups, capped for the wide k) would push a small batch's K3b pilot down to the K1 one
+        L.pilot_part = L.partials;
+        L.pilot_part_lists = ncand / k;
+    }
     uint64_t *keys = (uint64_t *)(ws + w.keys);
     L.metric = c->metric;
     L.data = (const float *)c->d_data;
@@ -402,7 +426,7 @@ int run_search(wvg_corpus *c, const void *d_q, uint32_t qpitch, uint32_t nq, uin
         a.cache_tail256 = 0;
     }
     if (p.screen) {
-        if (ensure_shadow(c, s)) {
+        if (ensure_shadow(c, s) && !(p.wide && c->sh_i8)) {  // (K3c-W reads the bf16 shadow only)
             ProfArm arm(c->ctx);
             if (arm.rc) return arm.rc;
             return run_screen(c, a, p, reinterpret_cast<char *>(partials), ids, dists, counts, s);

@@ -29,7 +29,9 @@ class Context:
     the others keep wvg_options_default's values.  batch_screen: 2 (default)
     int8 / bf16 screen for dot / cosine batches and the bf16 screen for
     l2-squared ones, 1 bf16 everywhere, 0 exact only, 3 as 2 with the int8
-    screen for l2-squared batches at d = 512 / 768 / 1024 too (K3i-L2).
+    screen for l2-squared batches at d = 512 / 768 / 1024 too (K3i-L2), 4
+    the bf16 screen everywhere (no int8 screens) and its wide form K3c-W for
+    batches at 16 < k <= 256.
     cache_reuse: 1 (default), 0 streaming, 2 as 1 with the slice-wise shared scan
     for PQ codebooks beyond LDS (m >= 96 at ks = 256) in pipelined calls."""
 

@@ -119,6 +119,17 @@ typedef struct wvg_options {
                                   100 / 256: cosine 32.5 / 220 / 297 ms against 124 / 248 / 288 ms,
                                   l2-squared 45 / 271 / 328 ms against 1017 / 1020 / 1086 ms; 64-query
                                   batches on a 1M x 128 corpus at k <= 100 are up to 0.3 ms slower.
+                                  5 (opt-in): as 2 for every F32 corpus; on a BQ corpus of up to 4096
+                                  bits, wvg_search / wvg_search_device batches of at least
+                                  max(2, mfma_min_queries) queries at k <= 256, with no allow list or one
+                                  shared by the batch, are scored on the int8 matrix cores (K5m: Hamming
+                                  = sum a * s + popcount(q), exact in int32; ids, distance bits, counts
+                                  and padding identical to the default route; no shadow).  Every other
+                                  BQ call keeps its route.  Measured with 1024-query batches against the
+                                  default route: 100M x 1536 171.6 (k = 10) / 191.0 (k = 200) against
+                                  2633 / 2643 ms, 10M x 1536 k = 200 26.8 against 87.8 ms (64 queries:
+                                  4.72 against 5.52 ms); slower at 1M x 768 (5.38 against 5.30 ms) and at
+                                  10M x 128 (17.0 against 13.1 ms).
                                   The first screened search of a corpus allocates its shadow: int8 = dim
                                   + 8 bytes per row of capacity (7.7 GB at 10M x 768; its first build
                                   also takes one pass over the rows for the corpus scale and one host
@@ -391,7 +402,12 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  *   + the sort's temporary storage for k entries
  *   + the queries' codes or LUTs for all nq queries, as for k <= 256,
  * every piece rounded up to 256 bytes, slots = 64 x the corpus's tiles.  The
- * pipelined, grouped and multi-GPU entry points keep k <= 256.             */
+ * pipelined, grouped and multi-GPU entry points keep k <= 256.
+ * A BQ corpus in a batch_screen = 5 context: the larger of the default
+ * route's bytes and K5m's -- partial lists nq x ranges x k x 8, the survivor
+ * pools ranges x padded nq x (2 max(k, 64) + 256) x 8 (at most 256 MiB), the
+ * queries' +-1 image padded nq x ceil(dim / 512) x 512 bytes and 4 bytes per
+ * padded query -- plus the queries' codes as before.                        */
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k);
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                       uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
@@ -582,7 +598,12 @@ int wvg_search_device_pipelined_shadow(wvg_corpus *c, uint32_t nq, uint32_t k, u
  * d = 512 / 768 / 1024 the int8 screen, 2, with dim + 8 shadow bytes per row
  * (1 again once the corpus's shadow fell back to bf16), and no matrix path at
  * all elsewhere); BQ / PQ corpora, other metrics, smaller batches, k > 256, an
- * empty corpus, nq == 0 or k == 0: all zero.  shared_allow_list != 0: the
+ * empty corpus, nq == 0 or k == 0: all zero -- except a BQ corpus of up to 4096
+ * bits in a batch_screen = 5 context, whose batches of at least
+ * max(2, mfma_min_queries) queries at k <= 256 report matrix = 1, screen = 0,
+ * shadow_bytes_per_row = 0 (K5m: exact distances from int8 MFMA, nothing
+ * allocated per corpus) and, in `reserved`, the row ranges the kernel splits
+ * the corpus into (0 on every other route).  shared_allow_list != 0: the
  * batch carries one allow list for all its queries; the route is the same.
  * Per-query allow windows never take the matrix path.                      */
 typedef struct wvg_batch_plan {

@@ -167,7 +167,8 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s);
 inline bool shadow_wants_i8(const wvg_corpus *c)
 {
     const int bs = c->ctx->opt.batch_screen;
-    return (c->metric == WVG_METRIC_L2 ? bs == 3 : bs == 2 || bs == 3) && wvg::screen_i8_supported(c->dim);
+    // (5 is 2 for every F32 corpus: it only moves BQ batches to K5m)
+    return (c->metric == WVG_METRIC_L2 ? bs == 3 : bs == 2 || bs == 3 || bs == 5) && wvg::screen_i8_supported(c->dim);
 }
 
 // ---- search planning (wvg_search.hip) ------------------------------------------
@@ -194,6 +195,8 @@ struct SearchPlan {
     uint32_t fb_groups = 0; // screen: K1 workgroups per flagged query's rescan
     uint32_t kbn = 0;       // screen: 32-element K blocks
     bool cosched = false; // PQ batch: co-scheduled K8e (ScanArgs::cosched)
+    bool bqm = false;     // BQ batch on the int8 MFMA kernel (K5m, batch_screen = 5; plan_bq_mfma): groups = its
+    size_t bqm_bytes = 0; // row ranges, bqm_bytes its workspace (bq_mfma_ws)
     int mq = 0;           // F32 co-scheduled batch: queries per K1Q workgroup (0 = one, the COS K1)
     bool empty = false;
     const uint64_t *allow_host = nullptr;  // the caller's allow words of tiles [tb, te), or null
@@ -208,6 +211,7 @@ struct SearchPlan {
     }
     size_t workspace_bytes(uint32_t nq, uint32_t k) const
     {
+        if (bqm) return bqm_bytes;
         if (screen) return std::max(screen_ws(nq, k, (uint32_t)groups, kbn, fb_groups, wide).total, gemm_bytes(nq, k, exact_groups, gemm));
         return gemm_bytes(nq, k, groups, gemm);
     }
@@ -218,6 +222,10 @@ bool allow_tile_range(const wvg_corpus *c, const uint64_t *allow, uint64_t allow
 // per-query allow windows, ScanArgs::allow_qstride)
 SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *allow, uint64_t allow_words,
                        bool mq_ok = true, bool gemm_ok = true);
+// K5m: moves the plan of a BQ batch of wvg_search / wvg_search_device (one shared allow list or none) to
+// the int8 MFMA kernel where it applies -- a batch_screen = 5 context, nq >= max(2, mfma_min_queries > 0),
+// k <= 256, dim <= 4096, pools that fit -- and leaves every other plan as it is.
+void plan_bq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k);
 uint32_t next_direction(wvg_corpus *c, uint32_t nq);
 int pq_dense(const wvg_corpus *c, const uint64_t *d_allow);
 void prepare_queries_host(const wvg_corpus *c, const float *queries, uint32_t nq, std::vector<float> &qf,

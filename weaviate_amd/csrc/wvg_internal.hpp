@@ -474,6 +474,31 @@ hipError_t launch_scan_bq(const ScanArgs &a, uint64_t *partials, int groups, hip
 constexpr int BQ_SCAN_WAVES = 4;
 constexpr size_t BQ_EMIT_LDS_MAX = 128u << 10;
 hipError_t launch_scan_bq_emit(const ScanArgs &a, uint64_t *partials, int groups, bool lds, hipStream_t s);
+// K5m (wvg_bq_mfma.hip; a batch_screen = 5 context): a batch of BQ queries scored with int8 MFMAs,
+// hamming = sum a * s + popcount(q) exactly.  Dimensions up to 4096 bits (64 queries per workgroup up to
+// 2048, 32 above: the block's +-1 image stays in LDS), k <= 256.  ranges: row ranges of at least 2048
+// rows, one workgroup per CU per query block, the (workgroup, query) survivor pools -- bq_mfma_pool(k)
+// keys each -- within 256 MiB; 0 = the pools of even one range do not fit (the batch keeps K5).
+bool bq_mfma_supported(uint32_t dim, uint32_t k);
+uint32_t bq_mfma_qblock(uint32_t dim);
+uint32_t bq_mfma_pool(uint32_t k);
+uint32_t bq_mfma_ranges(uint32_t nq, uint32_t k, uint32_t dim, uint64_t ntiles, int num_cus);
+struct BqMfmaWs {  // byte offsets: partial lists [nq][ranges][k] first, as every route's
+    size_t part = 0, pools = 0, image = 0, pc = 0, total = 0;
+};
+BqMfmaWs bq_mfma_ws(uint32_t nq, uint32_t k, uint32_t dim, uint32_t ranges);
+struct BqMfmaLaunch {
+    const void *data;       // the corpus's tiled codes
+    const uint64_t *valid;
+    const uint64_t *allow;  // one list shared by the batch, or null (ScanArgs::allow, allow_words, allow_t0)
+    uint64_t allow_words, allow_t0, tile_begin, tile_end;
+    uint32_t dim, nchunks;
+    const uint64_t *qcodes;  // the queries' sign bits, qpitch words apart
+    uint32_t qpitch, nq, k, ranges;
+    char *ws;                // bq_mfma_ws(nq, k, dim, ranges).total bytes
+};
+// the query image, then the scoring kernel; the caller merges ws + part with launch_merge_keys
+hipError_t launch_bq_mfma(const BqMfmaLaunch &L, hipStream_t s);
 // Shared-row query stream of a BQ corpus (scan_bq_qshare_kernel, wvg_bq_qshare.hip): one launch of
 // (groups, passes) 4-wave workgroups; pass p scores queries [p Q, min(nq, (p + 1) Q)), Q =
 // bq_qshare_queries_per_pass(), against every tile of its range, each tile loaded once, in direction

@@ -307,6 +307,20 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
     return p;
 }
 
+void plan_bq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k)
+{
+    const uint32_t mn = c->ctx->opt.mfma_min_queries;
+    if (p.empty || c->kind != WVG_KIND_BQ || c->ctx->opt.batch_screen != 5 || mn == 0 || nq < mn || nq < 2 ||
+        !bq_mfma_supported(c->dim, k))
+        return;
+    const uint32_t r = bq_mfma_ranges(nq, k, c->dim, std::max<uint64_t>(1, p.te - p.tb), c->ctx->num_cus);
+    if (r == 0) return;
+    p.bqm = true;
+    p.cosched = false;
+    p.groups = (int)r;
+    p.bqm_bytes = bq_mfma_ws(nq, k, c->dim, r).total;
+}
+
 // K3c: screen, exact rescore of the candidates, top-k; the flagged queries
 // (a range list overflowed below tau) are rescanned exactly with K1.
 static int run_screen(wvg_corpus *c, const ScanArgs &a, const SearchPlan &p, char *ws, uint64_t *ids, float *dists,
@@ -482,6 +496,27 @@ int run_search(wvg_corpus *c, const void *d_q, uint32_t qpitch, uint32_t nq, uin
     }
     ProfArm arm(c->ctx);
     if (arm.rc) return arm.rc;
+    if (p.bqm) {  // K5m: d_q = the queries' sign bits; exact keys per (query, range), unsorted
+        BqMfmaLaunch L{};
+        L.data = c->d_data;
+        L.valid = c->d_valid;
+        L.allow = d_allow;
+        L.allow_words = a.allow_words;
+        L.allow_t0 = a.allow_t0;
+        L.tile_begin = p.tb;
+        L.tile_end = p.te;
+        L.dim = c->dim;
+        L.nchunks = c->nchunks;
+        L.qcodes = (const uint64_t *)d_q;
+        L.qpitch = qpitch;
+        L.nq = nq;
+        L.k = k;
+        L.ranges = (uint32_t)p.groups;
+        L.ws = reinterpret_cast<char *>(partials);
+        WVG_HIP(launch_bq_mfma(L, s));
+        WVG_HIP(launch_merge_keys(partials, nq, (uint32_t)p.groups * k, k, c->id_base, ids, dists, counts, s));
+        return WVG_OK;
+    }
     if (p.gemm) {
         uint32_t *prog = reinterpret_cast<uint32_t *>(partials + (size_t)nq * p.groups * k);
         WVG_HIP(launch_gemm_topk(a, (uint32_t)p.groups, partials, prog, prog + (size_t)p.groups * ((nq + 15) / 16),
@@ -931,6 +966,7 @@ static int wvg::search_batch(wvg_corpus *c, const float *queries, uint32_t nq, u
     }
     if (k > MAX_K)  // beyond the fused register top-k: select + sort in HBM
         return search_large_k(c, queries, nq, k, allow_bits, allow_words, p, out_ids, out_dists, out_counts);
+    plan_bq_mfma(c, p, nq, k);
     SlotGuard g(c->ctx);
     rc = c->ctx->acquire(&g.slot);
     if (rc) return rc;
@@ -1576,9 +1612,11 @@ int wvg_search_batch_plan(wvg_corpus *c, uint32_t nq, uint32_t k, int shared_all
     std::shared_lock<std::shared_mutex> lk(c->rw);
     // one allow list shared by the batch masks tiles inside the same kernels: the route does not depend on it
     (void)shared_allow_list;
-    const SearchPlan p = plan_search(c, nq, k, nullptr, 0);
+    SearchPlan p = plan_search(c, nq, k, nullptr, 0);
     if (p.empty) return WVG_OK;
-    out->matrix = p.gemm || p.screen;
+    plan_bq_mfma(c, p, nq, k);
+    out->matrix = p.gemm || p.screen || p.bqm;
+    if (p.bqm) out->reserved = (uint32_t)p.groups;  // K5m's row ranges (exact keys: no screen, no shadow)
     if (p.screen) {
         // the shadow a first screened search would build (ensure_shadow), or the one that exists
         const bool i8 = c->d_shadow ? c->sh_i8 : shadow_wants_i8(c);
@@ -1597,7 +1635,10 @@ size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
     }
     const uint32_t kk = std::max<uint32_t>(k, 1);
     SearchPlan p = plan_search(c, nq, k, nullptr, 0);
-    const size_t dev = WS_STATUS_BYTES + align_up(p.workspace_bytes(nq, kk), 256) + device_query_bytes(c, nq);
+    size_t part = p.workspace_bytes(nq, kk);
+    plan_bq_mfma(c, p, nq, k);  // (K5m: the larger of K5's layout and its own)
+    part = std::max(part, p.workspace_bytes(nq, kk));
+    const size_t dev = WS_STATUS_BYTES + align_up(part, 256) + device_query_bytes(c, nq);
     if (c->kind == WVG_KIND_BQ) {  // pipelined: the shared-row layout, or the per-query launches' (it only grows)
         const SearchPlan pb = plan_search(c, 1, k, nullptr, 0);
         const size_t shared = bq_stream_layout(c, nq, kk, bq_qshare_groups(pb.te - pb.tb, c->ctx->num_cus)).total;
@@ -2056,6 +2097,7 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
         return dsel_search(c, d_queries, nq, k, p, d_ids, d_dists, d_counts, (char *)d_workspace + WS_STATUS_BYTES,
                            workspace_bytes - WS_STATUS_BYTES, s);
     }
+    plan_bq_mfma(c, p, nq, k);
     const size_t part = align_up(p.workspace_bytes(nq, k), 256);
     if (!d_workspace || workspace_bytes < WS_STATUS_BYTES + part + device_query_bytes(c, nq))
         return fail(WVG_ERR_INVALID, "workspace too small");
@@ -2070,6 +2112,8 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
         const uint32_t words = bq_words(c->dim), qpitch = bq_chunks(c->dim) * 2;
         uint64_t *codes = (uint64_t *)(qbuf + align_up((size_t)nq * qpitch * 8, 256));
         WVG_HIP(launch_bq_encode_rows(d_queries, nq, c->dim, 0, codes, s));
+        if (p.bqm)  // K5m's prologue reads the encoder's dense codes
+            return run_search(c, codes, words, nq, k, nullptr, p, partials, d_ids, d_dists, d_counts, s);
         WVG_HIP(hipMemsetAsync(qbuf, 0, (size_t)nq * qpitch * 8, s));
         WVG_HIP(hipMemcpy2DAsync(qbuf, (size_t)qpitch * 8, codes, (size_t)words * 8, (size_t)words * 8, nq,
                                  hipMemcpyDeviceToDevice, s));

@@ -31,7 +31,9 @@ class Context:
     l2-squared ones, 1 bf16 everywhere, 0 exact only, 3 as 2 with the int8
     screen for l2-squared batches at d = 512 / 768 / 1024 too (K3i-L2), 4
     the bf16 screen everywhere (no int8 screens) and its wide form K3c-W for
-    batches at 16 < k <= 256.
+    batches at 16 < k <= 256, 5 as 2 for F32 corpora, and batches of at
+    least mfma_min_queries queries on a BQ corpus (k <= 256, d <= 4096) score
+    on the int8 matrix cores (K5m), results bit-identical to the default route.
     cache_reuse: 1 (default), 0 streaming, 2 as 1 with the slice-wise shared scan
     for PQ codebooks beyond LDS (m >= 96 at ks = 256) in pipelined calls."""
 

@@ -882,13 +882,49 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) __attribute__((amdgpu_waves_per_eu
 // Results do not depend on the bound's slack (the argument at the top of the file holds for any sound
 // bound): a pair that is not admitted holds no key below tau.
 //
-// The rounds are the screened form's with the row fetched on demand: a lane takes its lowest admitted pair
-// (rg, r), loads row 16 rg + (l & 15) of tile t from a.data -- 32 chunks 1 KiB apart, default policy, only
-// lanes that hold a pair -- and runs the unchanged chain against query 4 (l >> 4) + r from the fp32 LDS
-// image; the key is built from (t, row).  A pair belongs to exactly one lane, so keys stay unique; a lane
-// with two pairs on one row loads it twice (the second read hits cache).
+// Packed rounds.  The exact chain of an admitted pair reads its row by address, so nothing ties it to the
+// tile that admitted it.  On the bench's shape a tile admits about 3 pairs and a wave walks about 8 tiles:
+// a round per tile runs the 32-chunk chain, two gather latencies and the 16-way offer loop for 3 working
+// lanes of 64, and the next tile's loads wait behind it.  (Measured, profiles/qshare_packed_rounds/: a
+// third fewer VALU instructions, 6-7 % of the launch at 2 to 8 queries, under 1 % at 16, where the gathered
+// rows' traffic and not the rounds' latency is what a query costs.)
+// So a tile only APPENDS its admitted pairs to a
+// queue of the wave in LDS -- a 32-bit entry (tile position i in the wave's range, row 0..63, query 0..15
+// of the pass); per admission bit one ballot, skipped wave-uniformly when empty, and one store per holding
+// lane at the wave-uniform count + the lane's rank in the ballot -- and rounds run when they are full:
+// while 64 entries are pending, until the queue is empty after the last tile of the pass, and until it is
+// empty after a tile that admitted QSP_LOOSE pairs or more (a list whose tau is still falling fast -- an
+// open seed, a filtered query whose sample was empty -- would otherwise screen its next tiles under a
+// stale bound and gather rows for nothing: with 16 disjoint range lists the launch took 127 us without this
+// rule, 123 us at 16 pairs and 111.5 us at 8, against 117 us with a round per tile; at 8 a seeded wave of
+// the bench's shape, 3.3 pairs a tile, takes the early exit in about 2 % of its tiles).  In a round
+// lane l takes entry (top - 64 + l), loads row `row` of tile t(i) from a.data -- 32 chunks 1 KiB apart,
+// default policy, only lanes that hold an entry -- through the ring of 16 chunks and runs the unchanged
+// chain against its entry's query from the fp32 LDS image; the key is built from (t(i), row); the unrolled
+// 16-query ballot loop offers it (tk[] is never indexed dynamically).  Entries leave from the top, so
+// nothing is moved; at most 63 stay pending and a tile adds at most 16 x 64, hence QSP_CAP and no
+// overflow path.  An entry holds i modulo 2^QSP_IBITS: the queue is also emptied after the last tile of
+// every block of 2^QSP_IBITS positions, so pending entries never span two blocks.
+// Why no result changes:
+//  - a pair is appended exactly once and an entry belongs to one lane of one round, so every key is
+//    produced once and keys stay unique;
+//  - the chain is the same lane-wise instruction sequence on the same operands (the row's chunks, the
+//    query's chunks from qfsh) whichever lane and round runs it;
+//  - a list is the set of the k smallest unique keys below its bound among the keys offered, whatever
+//    the order and the batches (the argument at the top of the file): the lists at the end of a pass
+//    are those of the per-tile rounds;
+//  - a pair admitted under a tau that an earlier drain would have lowered is only an extra offer, dropped
+//    at offer_bounded's ballot; no pair is skipped that the per-tile rounds would have scored below tau,
+//    because tau only falls and the screen is applied with the tau of its moment or a larger one;
+//  - an open tau, NaN / +-inf rows and queries still admit: an open query appends 64 entries per tile, so
+//    the queue is emptied and its list tightens after every tile, as the per-tile rounds did.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int QSP_CAP = 63 + 16 * 64;  // entries of a wave's queue: 63 left pending + one fully admitted tile
+constexpr int QSP_IBITS = 22;          // an entry: i mod 2^22 << 10 | row << 4 | query
+constexpr uint64_t QSP_IMASK = (1ull << QSP_IBITS) - 1;
+constexpr int QSP_LOOSE = 8;           // pairs of one tile from which the queue is emptied at once (seeded lists on
+                                       // the bench's shape admit 3.3 a tile; a list that is still filling, dozens)
 
 template <bool NT>
 __device__ __forceinline__ bf16x8 ld_frag(const uint4 *p)
@@ -932,8 +968,10 @@ __device__ __forceinline__ void qshare_shadow_body(const QShareArgs &a, const QS
     const uint32_t qstride = a.qpitch / 4;
     const float hg = a.hg;
     __shared__ f4v qfsh[QP * QS_FROW];  // the pass's fp32 queries (the rounds' operands)
+    __shared__ uint32_t pend_sh[SCAN_WAVES][QSP_CAP];  // the waves' pending pairs ("Packed rounds" above)
+    uint32_t *pend = pend_sh[wave_id()];
 #ifdef WVG_TOOLS
-    uint32_t n_fold = 0, n_pairs = 0, n_rounds = 0, n_adm = 0;  // as qshare_scan_body's
+    uint32_t n_fold = 0, n_pairs = 0, n_rounds = 0, n_adm = 0;  // as qshare_scan_body's (n_rounds: packed rounds)
 #endif
     for (uint32_t q0 = 0, pass = 0; q0 < a.nq; q0 += QP, pass++) {
         const uint32_t nqp = a.nq - q0 < (uint32_t)QP ? a.nq - q0 : (uint32_t)QP;
@@ -942,6 +980,7 @@ __device__ __forceinline__ void qshare_shadow_body(const QShareArgs &a, const QS
         WaveTopK<1> tk[QP];
 #pragma unroll
         for (int j = 0; j < QP; j++) tk[j].init_bounded((int)a.k, (uint32_t)j < nqp ? seed_bound(sd + j) : WVG_KEY_NONE);
+        uint32_t npend = 0u;  // wave-uniform: the queue's entries; 0 at the start and at the end of every pass
         {  // the fp32 queries into LDS, two chunks per thread: thread = (query, chunk), (query + QP / 2, chunk)
             uint32_t tid = threadIdx.x;
             asm volatile("" : "+v"(tid));
@@ -1000,89 +1039,104 @@ __device__ __forceinline__ void qshare_shadow_body(const QShareArgs &a, const QS
                 m_next = valid[rev ? t - 1 : t + 1];
                 if constexpr (FILT) pass_allow_words<QP>(aw_next, al, f.stride, f.t0, rev ? t - 1 : t + 1, nqp);
             }
-            if (many == 0ull) continue;  // wave-uniform: nothing live (FILT: and allowed) in this tile
-            const uint4 *sp = shadow + (size_t)t * (16 * 64) + lane;
-            bf16x8 xb[4][4];
-            if (i >= split) {
+            const uint32_t npend0 = npend;
+            if (many != 0ull) {  // wave-uniform: something live (FILT: and allowed) in this tile
+                const uint4 *sp = shadow + (size_t)t * (16 * 64) + lane;
+                bf16x8 xb[4][4];
+                if (i >= split) {
 #pragma unroll
-                for (int fr = 0; fr < 16; fr++) xb[fr >> 2][fr & 3] = ld_frag<false>(sp + fr * 64);
-            } else {
+                    for (int fr = 0; fr < 16; fr++) xb[fr >> 2][fr & 3] = ld_frag<false>(sp + fr * 64);
+                } else {
 #pragma unroll
-                for (int fr = 0; fr < 16; fr++) xb[fr >> 2][fr & 3] = ld_frag<true>(sp + fr * 64);
-            }
-            float nx[4];
+                    for (int fr = 0; fr < 16; fr++) xb[fr >> 2][fr & 3] = ld_frag<true>(sp + fr * 64);
+                }
+                float nx[4];
 #pragma unroll
-            for (int rg = 0; rg < 4; rg++) nx[rg] = a.norms[(size_t)t * 64 + 16 * rg + (lane & 15)];
-            // tau of the lane's four queries, as a distance (NaN for an open tau)
-            float taud[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                uint32_t hi = (uint32_t)(tk[r].tau >> 32);
-#pragma unroll
-                for (int g = 1; g < 4; g++) hi = (lane >> 4) == g ? (uint32_t)(tk[4 * g + r].tau >> 32) : hi;
-                taud[r] = wvg_unord_f32(hi);
-            }
-            floatx4 acc[4];
-#pragma unroll
-            for (int rg = 0; rg < 4; rg++) acc[rg] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int kb = 0; kb < 4; kb++)
-#pragma unroll
-                for (int rg = 0; rg < 4; rg++)
-                    acc[rg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kb], xb[kb][rg], acc[rg], 0, 0, 0);
-            uint32_t adm = 0u;
-#pragma unroll
-            for (int rg = 0; rg < 4; rg++) {
-                const float nrm = nx[rg];
-                const float h = nrm <= 0x1p60f ? (nrm * nrm) * hg : __builtin_nanf("");
+                for (int rg = 0; rg < 4; rg++) nx[rg] = a.norms[(size_t)t * 64 + 16 * rg + (lane & 15)];
+                // tau of the lane's four queries, as a distance (NaN for an open tau)
+                float taud[4];
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    // the pair's live lanes: row 16 rg + i valid (FILT: and allowed by query 4 g + r), the query in the pass
-                    uint64_t live;
-                    if constexpr (FILT) {
-                        live = field16(mq[r], rg) | field16(mq[4 + r], rg) << 16 | field16(mq[8 + r], rg) << 32 |
-                               field16(mq[12 + r], rg) << 48;  // (mq[j] = 0 past nqp)
-                    } else {
-                        live = (field16(m, rg) * 0x0001000100010001ull) & qlive[r];
-                    }
-                    if (live == 0ull) continue;  // wave-uniform
-                    const float e1 = __builtin_fmaf(nrm, k1[r], k2[r]);
-                    const float u = (acc[rg][r] - h) + e1;
-                    float lower = cq[r] - 2.0f * u;
-                    lower = lower != lower ? -__builtin_inff() : __builtin_fmaxf(lower, 0.0f);
-                    const bool skip = (lower > taud[r] && lower < __builtin_inff()) || !__builtin_amdgcn_inverse_ballot_w64(live);
-                    adm |= skip ? 0u : 1u << (4 * rg + r);
+                    uint32_t hi = (uint32_t)(tk[r].tau >> 32);
+#pragma unroll
+                    for (int g = 1; g < 4; g++) hi = (lane >> 4) == g ? (uint32_t)(tk[4 * g + r].tau >> 32) : hi;
+                    taud[r] = wvg_unord_f32(hi);
                 }
-            }
+                floatx4 acc[4];
+#pragma unroll
+                for (int rg = 0; rg < 4; rg++) acc[rg] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int kb = 0; kb < 4; kb++)
+#pragma unroll
+                    for (int rg = 0; rg < 4; rg++)
+                        acc[rg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kb], xb[kb][rg], acc[rg], 0, 0, 0);
+                // admission, and the append of the admitted pairs: pair (rg, r) of lane l is (row 16 rg + (l & 15),
+                // query 4 (l >> 4) + r); per pair one ballot, skipped wave-uniformly when empty, and one store per
+                // holding lane at the wave-uniform count + its rank in the ballot
+                const uint32_t ent = (uint32_t)(i & QSP_IMASK) << 10 | (uint32_t)(lane & 15) << 4 | jg;
 #ifdef WVG_TOOLS
-            n_pairs += nqp;
-            n_adm += (uint32_t)__builtin_popcount(adm);
-            {  // (query, tile) pairs with an admitted row: query 4 g + r over the lanes of group g
-                uint32_t any = 0u;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const uint64_t b = __ballot((adm & (0x1111u << r)) != 0u);
-#pragma unroll
-                    for (int g = 0; g < 4; g++) any |= ((b >> (16 * g)) & 0xFFFFull) != 0ull ? 1u << (4 * g + r) : 0u;
-                }
-                n_fold += (uint32_t)__builtin_popcount(any);
-            }
+                uint32_t any = 0u;  // (query, tile) pairs with an admitted row: query 4 g + r over the lanes of group g
+                n_pairs += nqp;
 #endif
-            const float4 *tp = data + (size_t)t * NC * 64 + (lane & 15);
-            while (true) {
-                const uint64_t took_any = __ballot(adm != 0u);  // the lanes that score a pair in this round
-                if (took_any == 0ull) break;  // wave-uniform
+#pragma unroll
+                for (int rg = 0; rg < 4; rg++) {
+                    const float nrm = nx[rg];
+                    const float h = nrm <= 0x1p60f ? (nrm * nrm) * hg : __builtin_nanf("");
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        // the pair's live lanes: row 16 rg + i valid (FILT: and allowed by query 4 g + r), the query in the pass
+                        uint64_t live;
+                        if constexpr (FILT) {
+                            live = field16(mq[r], rg) | field16(mq[4 + r], rg) << 16 | field16(mq[8 + r], rg) << 32 |
+                                   field16(mq[12 + r], rg) << 48;  // (mq[j] = 0 past nqp)
+                        } else {
+                            live = (field16(m, rg) * 0x0001000100010001ull) & qlive[r];
+                        }
+                        if (live == 0ull) continue;  // wave-uniform
+                        const float e1 = __builtin_fmaf(nrm, k1[r], k2[r]);
+                        const float u = (acc[rg][r] - h) + e1;
+                        float lower = cq[r] - 2.0f * u;
+                        lower = lower != lower ? -__builtin_inff() : __builtin_fmaxf(lower, 0.0f);
+                        // (masks combined on the scalar side: written with && / || the lanes branched)
+                        const uint64_t hold = ~(__ballot(lower > taud[r]) & __ballot(lower < __builtin_inff())) & live;
+                        if (hold == 0ull) continue;  // wave-uniform
+                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hold >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hold, 0u));
+                        if ((hold >> lane) & 1ull) pend[npend + rank] = ent + (uint32_t)(rg << 8 | r);
+                        npend += (uint32_t)__popcll(hold);  // <= 63 + 1,024 = QSP_CAP: at most 63 were left pending
+#ifdef WVG_TOOLS
+                        n_adm += (uint32_t)__popcll(hold);
+#pragma unroll
+                        for (int g = 0; g < 4; g++) any |= ((hold >> (16 * g)) & 0xFFFFull) != 0ull ? 1u << (4 * g + r) : 0u;
+#endif
+                    }
+                }
+#ifdef WVG_TOOLS
+                n_fold += (uint32_t)__builtin_popcount(any);
+#endif
+            }
+            // packed rounds: full ones while 64 pairs are pending; everything at the end of the range (the
+            // queue is empty at pass_combine_publish), before a tile whose position would alias an entry's
+            // QSP_IBITS-bit field (all pending entries then lie in the current 2^QSP_IBITS block), and after
+            // a tile that admitted QSP_LOOSE pairs or more (some tau is still loose: the next tile is
+            // screened under the bound these pairs leave, as with a round per tile)
+            const bool flush = i + 1 == n || ((i + 1) & QSP_IMASK) == 0ull || npend - npend0 >= (uint32_t)QSP_LOOSE;
+            const uint64_t iblock = i & ~QSP_IMASK;
+            while (npend >= 64u || (flush && npend != 0u)) {  // wave-uniform
 #ifdef WVG_TOOLS
                 n_rounds++;
 #endif
-                const bool has = adm != 0u;
-                const uint32_t b = has ? (uint32_t)__builtin_ctz(adm) : 0u;  // the lane's lowest admitted pair
-                adm &= adm - 1u;
-                const uint32_t jl = jg + (b & 3u), row = (b >> 2) * 16 + (uint32_t)(lane & 15);
+                const uint32_t take = npend < 64u ? npend : 64u;
+                npend -= take;  // the top `take` entries: nothing is moved, the order of the offers is free
+                const bool has = (uint32_t)lane < take;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the appends above, other lanes' stores
+                __builtin_amdgcn_wave_barrier();
+                const uint32_t e = has ? pend[npend + (uint32_t)lane] : 0u;
+                const uint32_t jl = e & 15u, row = (e >> 4) & 63u;
+                const uint64_t ie = iblock + (e >> 10), te = rev ? t1 - 1 - ie : t0 + ie;
                 uint64_t key = WVG_KEY_NONE;
                 if (has) {  // only lanes that hold a pair load
                     const f4v *ql = qfsh + jl * QS_FROW;
-                    const float4 *xr = tp + (b >> 2) * 16;
+                    const float4 *xr = data + (size_t)te * NC * 64 + row;
                     f2v c2[4][4];
 #pragma unroll
                     for (int r = 0; r < 4; r++)
@@ -1101,7 +1155,7 @@ __device__ __forceinline__ void qshare_shadow_body(const QShareArgs &a, const QS
                         chunk_update2<WVG_M_L2>(c2, c & 7, ql[c], x[c % RING]);
                         if (c + RING < NC) x[c % RING] = xr[(size_t)(c + RING) * 64];
                     }
-                    key =wvg_make_key(wrap_metric(a.metric, avx256_reduce2(c2)), (uint32_t)(t * 64 + row));
+                    key = wvg_make_key(wrap_metric(a.metric, avx256_reduce2(c2)), (uint32_t)(te * 64 + row));
                 }
 #pragma unroll
                 for (int j = 0; j < QP; j++) {
@@ -1114,9 +1168,7 @@ __device__ __forceinline__ void qshare_shadow_body(const QShareArgs &a, const QS
         pass_combine_publish<1, QP, true>(tk, nqp, a.k, a.partials, a.ready, (size_t)q0 * G + blockIdx.x, G, q0 + QP < a.nq);
     }
 #ifdef WVG_TOOLS
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n_adm += __shfl_xor(n_adm, off);
-    if (lane == 0 && n_pairs) {
+    if (lane == 0 && n_pairs) {  // (n_adm is wave-uniform here: the ballots' popcounts)
         atomicAdd((unsigned long long *)a.screen_count, ((unsigned long long)n_pairs << 32) | n_fold);
         atomicAdd((unsigned long long *)a.screen_count + 1, ((unsigned long long)n_rounds << 32) | n_adm);
     }

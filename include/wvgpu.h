@@ -130,6 +130,22 @@ typedef struct wvg_options {
                                   2633 / 2643 ms, 10M x 1536 k = 200 26.8 against 87.8 ms (64 queries:
                                   4.72 against 5.52 ms); slower at 1M x 768 (5.38 against 5.30 ms) and at
                                   10M x 128 (17.0 against 13.1 ms).
+                                  6 (opt-in): as 2 for every F32 corpus, the default route for BQ; on an
+                                  l2-squared PQ corpus with a codebook, wvg_search / wvg_search_device
+                                  batches of at least max(2, mfma_min_queries) queries at k <= 256, with
+                                  no allow list or one shared by the batch, take K8m where dim % 32 = 0,
+                                  dim / m is 4 or 8, m <= 64 and dim x ks x 2 + 128 x dim + 2576 bytes
+                                  fit 160 KiB of LDS (d = 128 at ks = 256: 80 KiB): a bf16 MFMA screen
+                                  over rows decoded in the kernel from the code bytes (|q|^2 + |x^|^2 -
+                                  2 q.x^, K3c-L2's proven bound) + the exact LUT rescore; ids, distance
+                                  bits, counts and padding identical to the default route; no shadow,
+                                  nothing kept per corpus (the row norms are recomputed in every call).
+                                  Every other PQ call keeps its route.  Measured with 1024-query batches on uniform random codes, 6 against the default route in alternating
+                                  processes: 100M x 128 m = 32, k = 10 223.6 against 346.8 ms (0.047 of the
+                                  bf16 peak over the whole call), 10M 28.7 against 31.8 ms, 10M m = 16
+                                  17.6 against 30.9 ms; SLOWER at 100M k = 200 (1161 against 427 ms), with
+                                  64 queries at 100M (k = 10 37.1 against 21.4 ms, k = 200 221 against
+                                  25.8 ms) and at 1M x 128 (4.82 against 3.80 ms).
                                   The first screened search of a corpus allocates its shadow: int8 = dim
                                   + 8 bytes per row of capacity (7.7 GB at 10M x 768; its first build
                                   also takes one pass over the rows for the corpus scale and one host
@@ -407,7 +423,16 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * route's bytes and K5m's -- partial lists nq x ranges x k x 8, the survivor
  * pools ranges x padded nq x (2 max(k, 64) + 256) x 8 (at most 256 MiB), the
  * queries' +-1 image padded nq x ceil(dim / 512) x 512 bytes and 4 bytes per
- * padded query -- plus the queries' codes as before.                        */
+ * padded query -- plus the queries' codes as before.
+ * A PQ corpus in a batch_screen = 6 context (K8m's batches): the larger of the
+ * default route's bytes and K8m's -- the survivor pools nq x ranges x (2 max(k,
+ * 64) + 256) x 8 (ranges lowered until ranges x padded nq x that is at most 256
+ * MiB; the rescored keys are written in place), the row-norm array 4 bytes per
+ * slot, the codebook's bf16 image dim x ks x 2 and its fp64 square sums m x ks x
+ * 8, the queries' fragments padded nq x dim x 2 and four constants of 4 bytes
+ * per padded query, per query a bound and a flag-list entry of 4 bytes, per
+ * (query, range) a count and a dropped bound of 4 bytes, and the rescan's partial
+ * lists nq x 32 x k x 8 -- plus the queries' LUTs nq x m x ks x 4 as before.   */
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k);
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                       uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
@@ -603,7 +628,10 @@ int wvg_search_device_pipelined_shadow(wvg_corpus *c, uint32_t nq, uint32_t k, u
  * max(2, mfma_min_queries) queries at k <= 256 report matrix = 1, screen = 0,
  * shadow_bytes_per_row = 0 (K5m: exact distances from int8 MFMA, nothing
  * allocated per corpus) and, in `reserved`, the row ranges the kernel splits
- * the corpus into (0 on every other route).  shared_allow_list != 0: the
+ * the corpus into (0 on every other route); and a PQ batch that takes K8m in a
+ * batch_screen = 6 context (the option's conditions) reports matrix = 1, screen
+ * = 1, shadow_bytes_per_row = 0 and its row ranges in `reserved`; every other PQ
+ * batch stays all zero.  shared_allow_list != 0: the
  * batch carries one allow list for all its queries; the route is the same.
  * Per-query allow windows never take the matrix path.                      */
 typedef struct wvg_batch_plan {

@@ -167,8 +167,9 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s);
 inline bool shadow_wants_i8(const wvg_corpus *c)
 {
     const int bs = c->ctx->opt.batch_screen;
-    // (5 is 2 for every F32 corpus: it only moves BQ batches to K5m)
-    return (c->metric == WVG_METRIC_L2 ? bs == 3 : bs == 2 || bs == 3 || bs == 5) && wvg::screen_i8_supported(c->dim);
+    // (5 and 6 are 2 for every F32 corpus: they only move BQ batches to K5m, PQ batches to K8m)
+    return (c->metric == WVG_METRIC_L2 ? bs == 3 : bs == 2 || bs == 3 || bs == 5 || bs == 6) &&
+           wvg::screen_i8_supported(c->dim);
 }
 
 // ---- search planning (wvg_search.hip) ------------------------------------------
@@ -197,7 +198,11 @@ struct SearchPlan {
     bool cosched = false; // PQ batch: co-scheduled K8e (ScanArgs::cosched)
     bool bqm = false;     // BQ batch on the int8 MFMA kernel (K5m, batch_screen = 5; plan_bq_mfma): groups = its
     size_t bqm_bytes = 0; // row ranges, bqm_bytes its workspace (bq_mfma_ws)
-    int mq = 0;           // F32 co-scheduled batch: queries per K1Q workgroup (0 = one, the COS K1)
+    bool pqm = false;     // PQ batch on the bf16 MFMA screen (K8m, batch_screen = 6; plan_pq_mfma): groups = its row
+    size_t pqm_bytes = 0; // ranges, pqm_bytes its workspace (pq_mfma_ws), pqm_q the batch's fp32 queries on the
+    const float *pqm_q = nullptr;  // device, pqm_qpitch floats apart (set by the caller that staged them)
+    uint32_t pqm_qpitch = 0;
+    int mq = 0;          // F32 co-scheduled batch: queries per K1Q workgroup (0 = one, the COS K1)
     bool empty = false;
     const uint64_t *allow_host = nullptr;  // the caller's allow words of tiles [tb, te), or null
     uint64_t allow_qstride = 0;            // per-query allow windows (ScanArgs::allow_qstride)
@@ -212,6 +217,7 @@ struct SearchPlan {
     size_t workspace_bytes(uint32_t nq, uint32_t k) const
     {
         if (bqm) return bqm_bytes;
+        if (pqm) return pqm_bytes;
         if (screen) return std::max(screen_ws(nq, k, (uint32_t)groups, kbn, fb_groups, wide).total, gemm_bytes(nq, k, exact_groups, gemm));
         return gemm_bytes(nq, k, groups, gemm);
     }
@@ -226,6 +232,9 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
 // the int8 MFMA kernel where it applies -- a batch_screen = 5 context, nq >= max(2, mfma_min_queries > 0),
 // k <= 256, dim <= 4096, pools that fit -- and leaves every other plan as it is.
 void plan_bq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k);
+// K8m: the same for an l2-squared PQ batch with a codebook in a batch_screen = 6 context, where
+// pq_mfma_supported(dim, m, ks, k) holds and the pools fit.
+void plan_pq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k);
 uint32_t next_direction(wvg_corpus *c, uint32_t nq);
 int pq_dense(const wvg_corpus *c, const uint64_t *d_allow);
 void prepare_queries_host(const wvg_corpus *c, const float *queries, uint32_t nq, std::vector<float> &qf,

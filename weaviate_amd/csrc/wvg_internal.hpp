@@ -499,6 +499,44 @@ struct BqMfmaLaunch {
 };
 // the query image, then the scoring kernel; the caller merges ws + part with launch_merge_keys
 hipError_t launch_bq_mfma(const BqMfmaLaunch &L, hipStream_t s);
+// K8m (wvg_pq_mfma.hip; a batch_screen = 6 context): a batch of l2-squared PQ queries screened with bf16
+// MFMAs over rows decoded in the kernel from the corpus's code bytes (|q - x^|^2 = |q|^2 + |x^|^2 - 2 q.x^),
+// then the exact LUT rescore of the survivors; flagged queries are rescanned with K8's sum.  dim % 32 = 0,
+// dsub in {4, 8}, m <= 64 (a row's code chunks stay in registers), k <= 256, and the codebook's bf16 image
+// beside the query block's fragments within the LDS: dim * ks * 2 + 128 * dim + PQM_TAIL <= 160 KiB.
+constexpr uint32_t PQM_TAIL = 64 * 4 * 10 + 16;  // per-query constants, counts, bounds and the two flag words
+constexpr uint32_t PQM_FB_GROUPS = 32;           // workgroups of a flagged query's rescan
+bool pq_mfma_supported(uint32_t dim, uint32_t m, uint32_t ks, uint32_t k);
+void pq_mfma_prepare();  // the screen kernels' LDS limit, once per process (wvg_search_workspace_size, the launch)
+// alpha of K8m's bound: r is the sequential fp32 sum of m LUT entries, each go_step's chain over dsub elements
+__device__ __host__ inline double pq_mfma_alpha(uint32_t m, uint32_t dsub)
+{
+    return (2.0 * (double)(m + dsub) + 20.0) * 0x1p-24;
+}
+uint32_t pq_mfma_ranges(uint32_t nq, uint32_t k, uint64_t ntiles, int num_cus);
+struct PqMfmaWs {  // byte offsets; the pools [nq][ranges][P] first (collect packs the candidates into them)
+    size_t pools = 0, norms = 0, image = 0, sq = 0, qfrag = 0, k1 = 0, k2 = 0, em = 0, cq = 0, gb = 0, nmax = 0;
+    size_t pcnt = 0, pdrop = 0, fl = 0, nf = 0, fbp = 0, total = 0;
+};
+PqMfmaWs pq_mfma_ws(uint32_t nq, uint32_t k, uint32_t dim, uint32_t m, uint32_t ks, uint32_t ranges, uint64_t ntiles);
+struct PqMfmaLaunch {
+    ScanArgs scan;          // the batch as K8 would scan it: queries = launch_pq_lut's LUTs [nq][m * ks], one
+                            // shared allow list or none
+    uint32_t dim;
+    const float *centers;   // [m][ks][dsub]
+    const float *queries;   // [nq][qpitch] fp32
+    uint32_t qpitch, ranges;
+    char *ws;               // pq_mfma_ws(...).total bytes
+};
+// norms, constants, screen, collect, rescore, merge and the flagged queries' rescan, all on s
+hipError_t launch_pq_mfma(const PqMfmaLaunch &L, uint64_t *ids, float *dists, uint32_t *counts, hipStream_t s);
+// K3c-W's collect over [nq][nrr][P] pools (wvg_screen.hip): candidates packed in place, flagged queries listed
+hipError_t launch_collect_pools(uint64_t *pools, const uint32_t *pcnt, const uint32_t *pdrop, uint32_t nq, uint32_t nrr,
+                                uint32_t P, uint32_t k, const float *emax, uint32_t *flist, uint32_t *nflag,
+                                const uint32_t *gbound, hipStream_t s);
+// K8's generic scan (LUTs read in global memory) of a device-resident query list: partials [f][groups][k]
+hipError_t launch_scan_pq_qlist(const ScanArgs &a, uint64_t *partials, int groups, const uint32_t *qlist,
+                                const uint32_t *nlist, uint32_t slots, hipStream_t s);
 // Shared-row query stream of a BQ corpus (scan_bq_qshare_kernel, wvg_bq_qshare.hip): one launch of
 // (groups, passes) 4-wave workgroups; pass p scores queries [p Q, min(nq, (p + 1) Q)), Q =
 // bq_qshare_queries_per_pass(), against every tile of its range, each tile loaded once, in direction
@@ -631,23 +669,27 @@ __device__ __forceinline__ float norm_upper(double ss)
 // the safe side.  A query whose norm bound is above 2^56 or not finite: K1 = +inf, Cq = -inf (no row skipped).
 // The batched screen (screen_qconst_l2_kernel) and the shared-row scan's prologue (wvg_qshare.hip) both
 // take them from here.
+// (the forms that take alpha serve a route whose exact chain is another one: K8m's, pq_mfma_alpha)
 __device__ __host__ inline double screen_l2_alpha(uint32_t dim) { return ((double)dim / 16.0 + 32.0) * 0x1p-24; }
-inline float screen_l2_hg(uint32_t dim)
-{
-    return (float)((1.0 - (screen_l2_alpha(dim) + 0x1p-18)) * 0.5 * (1.0 - 0x1p-23));
-}
-__device__ __forceinline__ float screen_l2_query_consts(double ss, uint32_t dim, float &K1, float &K2, float &C)
+inline float screen_l2_hg_alpha(double alpha) { return (float)((1.0 - (alpha + 0x1p-18)) * 0.5 * (1.0 - 0x1p-23)); }
+inline float screen_l2_hg(uint32_t dim) { return screen_l2_hg_alpha(screen_l2_alpha(dim)); }
+__device__ __forceinline__ float screen_l2_query_consts(double ss, uint32_t dim, double alpha, float &K1, float &K2,
+                                                        float &C)
 {
     const float nq_up = norm_upper(ss);
     const float c = 0x1p-7f + 0x1p-15f + (float)dim * 0x1p-21f;
     K1 = c * nq_up + 0x1p-120f;
     K2 = 0x1p-120f * nq_up + 0x1p-110f;
-    C = (float)(ss * (1.0 - 0x1p-19 - screen_l2_alpha(dim)) - 0x1p-100);
+    C = (float)(ss * (1.0 - 0x1p-19 - alpha) - 0x1p-100);
     if (!(nq_up <= 0x1p56f)) {
         K1 = __builtin_inff();
         C = -__builtin_inff();
     }
     return nq_up;
+}
+__device__ __forceinline__ float screen_l2_query_consts(double ss, uint32_t dim, float &K1, float &K2, float &C)
+{
+    return screen_l2_query_consts(ss, dim, screen_l2_alpha(dim), K1, K2, C);
 }
 uint32_t screen_row_ranges(uint32_t nq, uint64_t ntiles, int num_cus);
 #ifdef WVG_TOOLS

@@ -1727,6 +1727,47 @@ hipError_t launch_scan_pq(const ScanArgs &a, uint64_t *partials, int groups, hip
     return launch_pq_e<4>(a, partials, groups, s);
 }
 
+// The exact rescan of a query list (K8m's flagged queries): K8's generic form with the LUTs read in
+// global memory -- block (g, f) scans slice g for the listed queries f, f + gridDim.y, ... < *nlist;
+// partials [f][groups][k].  The sums are pq_row_sum's, K8's bits.
+template <int E>
+__global__ __launch_bounds__(PQ_SCAN_WAVES * 64) void scan_pq_qlist_kernel(ScanArgs a, uint64_t *partials,
+                                                                           const uint32_t *qlist, const uint32_t *nlist)
+{
+    const uint32_t nl = *nlist;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint4 *data = reinterpret_cast<const uint4 *>(a.data);
+    const uint64_t ntiles = a.tile_end - a.tile_begin;
+    const uint64_t total = (uint64_t)gridDim.x * PQ_SCAN_WAVES;
+    const uint64_t gw = (uint64_t)blockIdx.x * PQ_SCAN_WAVES + wave;
+    const uint64_t t0 = a.tile_begin + ntiles * gw / total, t1 = a.tile_begin + ntiles * (gw + 1) / total;
+    for (uint32_t f = blockIdx.y; f < nl; f += gridDim.y) {
+        const float *glut = reinterpret_cast<const float *>(a.queries) + (size_t)qlist[f] * a.qpitch;
+        WaveTopK<E> tk;
+        tk.init((int)a.k);
+        for (uint64_t t = t0; t < t1; ++t) {
+            const uint64_t msk = pq_tile_mask(a, t);
+            if (msk == 0ull) continue;
+            const float sum = pq_row_sum(data + (size_t)t * a.nchunks * 64 + lane, a.nchunks, a.pq_m, a.pq_ks, glut,
+                                         (uint64_t)lane);
+            tk.offer(((msk >> lane) & 1ull) ? wvg_make_key(wrap_metric(a.metric, sum), (uint32_t)(t * 64 + lane))
+                                            : WVG_KEY_NONE);
+        }
+        group_combine_store<E, PQ_SCAN_WAVES>(tk, partials + ((size_t)f * gridDim.x + blockIdx.x) * a.k);
+        __syncthreads();  // the combine's LDS is reused by the next listed query
+    }
+}
+
+hipError_t launch_scan_pq_qlist(const ScanArgs &a, uint64_t *partials, int groups, const uint32_t *qlist,
+                                const uint32_t *nlist, uint32_t slots, hipStream_t s)
+{
+    const dim3 grid(groups, slots), block(PQ_SCAN_WAVES * 64);
+    if (a.k <= 64) hipLaunchKernelGGL((scan_pq_qlist_kernel<1>), grid, block, 0, s, a, partials, qlist, nlist);
+    else if (a.k <= 128) hipLaunchKernelGGL((scan_pq_qlist_kernel<2>), grid, block, 0, s, a, partials, qlist, nlist);
+    else hipLaunchKernelGGL((scan_pq_qlist_kernel<4>), grid, block, 0, s, a, partials, qlist, nlist);
+    return hipGetLastError();
+}
+
 __global__ void pq_adc_rows_kernel(int metric, const float *lut, uint32_t m, uint32_t ks, const uint8_t *codes,
                                    uint64_t n, float *out)
 {

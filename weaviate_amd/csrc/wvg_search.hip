@@ -321,6 +321,22 @@ void plan_bq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k)
     p.bqm_bytes = bq_mfma_ws(nq, k, c->dim, r).total;
 }
 
+void plan_pq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k)
+{
+    const uint32_t mn = c->ctx->opt.mfma_min_queries;
+    if (p.empty || c->kind != WVG_KIND_PQ || !c->d_centers || c->metric != WVG_METRIC_L2 ||
+        c->ctx->opt.batch_screen != 6 || mn == 0 || nq < mn || nq < 2 || p.allow_qstride != 0 ||
+        c->pq_ds * c->pq_m != c->dim || !pq_mfma_supported(c->dim, c->pq_m, c->pq_ks, k))
+        return;
+    const uint64_t ntiles = std::max<uint64_t>(1, p.te - p.tb);
+    const uint32_t r = pq_mfma_ranges(nq, k, ntiles, c->ctx->num_cus);
+    if (r == 0) return;
+    p.pqm = true;
+    p.cosched = false;
+    p.groups = (int)r;
+    p.pqm_bytes = pq_mfma_ws(nq, k, c->dim, c->pq_m, c->pq_ks, r, ntiles).total;
+}
+
 // K3c: screen, exact rescore of the candidates, top-k; the flagged queries
 // (a range list overflowed below tau) are rescanned exactly with K1.
 static int run_screen(wvg_corpus *c, const ScanArgs &a, const SearchPlan &p, char *ws, uint64_t *ids, float *dists,
@@ -515,6 +531,20 @@ int run_search(wvg_corpus *c, const void *d_q, uint32_t qpitch, uint32_t nq, uin
         L.ws = reinterpret_cast<char *>(partials);
         WVG_HIP(launch_bq_mfma(L, s));
         WVG_HIP(launch_merge_keys(partials, nq, (uint32_t)p.groups * k, k, c->id_base, ids, dists, counts, s));
+        return WVG_OK;
+    }
+    if (p.pqm) {  // K8m: d_q = the queries' LUTs (the rescore's and the rescan's), p.pqm_q the queries themselves
+        if (!p.pqm_q) return fail(WVG_ERR_INVALID, "K8m without the batch's queries");
+        PqMfmaLaunch L{};
+        L.scan = a;
+        L.scan.reverse = 0;
+        L.dim = c->dim;
+        L.centers = c->d_centers;
+        L.queries = p.pqm_q;
+        L.qpitch = p.pqm_qpitch;
+        L.ranges = (uint32_t)p.groups;
+        L.ws = reinterpret_cast<char *>(partials);
+        WVG_HIP(launch_pq_mfma(L, ids, dists, counts, s));
         return WVG_OK;
     }
     if (p.gemm) {
@@ -967,6 +997,7 @@ static int wvg::search_batch(wvg_corpus *c, const float *queries, uint32_t nq, u
     if (k > MAX_K)  // beyond the fused register top-k: select + sort in HBM
         return search_large_k(c, queries, nq, k, allow_bits, allow_words, p, out_ids, out_dists, out_counts);
     plan_bq_mfma(c, p, nq, k);
+    plan_pq_mfma(c, p, nq, k);
     SlotGuard g(c->ctx);
     rc = c->ctx->acquire(&g.slot);
     if (rc) return rc;
@@ -1005,6 +1036,10 @@ static int wvg::search_batch(wvg_corpus *c, const float *queries, uint32_t nq, u
     } else {
         rc = stage_queries(c, g.slot, queries, nq, b + o_q, qpitch, (float *)(b + o_q), b + o_qtmp, &st);
         if (rc) return rc;
+        if (p.pqm) {  // K8m scores the queries themselves: stage_queries left them at the PQ pitch, dim
+            p.pqm_q = (const float *)(b + o_qtmp);
+            p.pqm_qpitch = c->dim;
+        }
     }
     const uint64_t *d_allow = nullptr;
     if (p.allow_host && inlaunch_single(c, nq, p) && p.allow_bytes() <= STAGE_MAX) {
@@ -1615,8 +1650,13 @@ int wvg_search_batch_plan(wvg_corpus *c, uint32_t nq, uint32_t k, int shared_all
     SearchPlan p = plan_search(c, nq, k, nullptr, 0);
     if (p.empty) return WVG_OK;
     plan_bq_mfma(c, p, nq, k);
-    out->matrix = p.gemm || p.screen || p.bqm;
+    plan_pq_mfma(c, p, nq, k);
+    out->matrix = p.gemm || p.screen || p.bqm || p.pqm;
     if (p.bqm) out->reserved = (uint32_t)p.groups;  // K5m's row ranges (exact keys: no screen, no shadow)
+    if (p.pqm) {  // K8m: a bf16 screen over rows decoded in the kernel (no shadow), its row ranges
+        out->screen = 1;
+        out->reserved = (uint32_t)p.groups;
+    }
     if (p.screen) {
         // the shadow a first screened search would build (ensure_shadow), or the one that exists
         const bool i8 = c->d_shadow ? c->sh_i8 : shadow_wants_i8(c);
@@ -1636,7 +1676,9 @@ size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k)
     const uint32_t kk = std::max<uint32_t>(k, 1);
     SearchPlan p = plan_search(c, nq, k, nullptr, 0);
     size_t part = p.workspace_bytes(nq, kk);
-    plan_bq_mfma(c, p, nq, k);  // (K5m: the larger of K5's layout and its own)
+    plan_bq_mfma(c, p, nq, k);  // (K5m / K8m: the larger of the default route's layout and their own)
+    plan_pq_mfma(c, p, nq, k);
+    if (p.pqm) pq_mfma_prepare();  // (so that a first device call can be captured)
     part = std::max(part, p.workspace_bytes(nq, kk));
     const size_t dev = WS_STATUS_BYTES + align_up(part, 256) + device_query_bytes(c, nq);
     if (c->kind == WVG_KIND_BQ) {  // pipelined: the shared-row layout, or the per-query launches' (it only grows)
@@ -2098,6 +2140,9 @@ int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32
                            workspace_bytes - WS_STATUS_BYTES, s);
     }
     plan_bq_mfma(c, p, nq, k);
+    plan_pq_mfma(c, p, nq, k);
+    p.pqm_q = d_queries;  // (K8m scores the queries themselves)
+    p.pqm_qpitch = c->dim;
     const size_t part = align_up(p.workspace_bytes(nq, k), 256);
     if (!d_workspace || workspace_bytes < WS_STATUS_BYTES + part + device_query_bytes(c, nq))
         return fail(WVG_ERR_INVALID, "workspace too small");

@@ -33,7 +33,11 @@ class Context:
     the bf16 screen everywhere (no int8 screens) and its wide form K3c-W for
     batches at 16 < k <= 256, 5 as 2 for F32 corpora, and batches of at
     least mfma_min_queries queries on a BQ corpus (k <= 256, d <= 4096) score
-    on the int8 matrix cores (K5m), results bit-identical to the default route.
+    on the int8 matrix cores (K5m), results bit-identical to the default route,
+    6 as 2 for F32 and BQ corpora, and batches of at least mfma_min_queries
+    queries on an l2-squared PQ corpus (k <= 256, dim % 32 = 0, dim / m 4 or 8,
+    m <= 64, the codebook's bf16 image in LDS) take a bf16 MFMA screen over rows
+    decoded in the kernel plus the exact LUT rescore (K8m), bit-identical too.
     cache_reuse: 1 (default), 0 streaming, 2 as 1 with the slice-wise shared scan
     for PQ codebooks beyond LDS (m >= 96 at ks = 256) in pipelined calls."""
 

@@ -172,7 +172,7 @@ type Options struct {
 	MFMAMinQueries uint32 // dot / cosine batches of at least this many queries use MFMA (default 32)
 	CacheReuse     int32  // 1: consecutive scans reuse the Infinity Cache (default); 0: streaming; 2: as 1, and PQ codebooks beyond LDS (m >= 96 at ks = 256) share code reads slice-wise in pipelined calls
 	MergeWaitUs    uint32 // query-stream merge wait bound (default 4 s)
-	BatchScreen    int32  // 2: int8 screen (d 512/768/1024, else bf16) + exact rescore (default); 1: bf16; 0: exact only; 3 (opt-in): as 2, and l2-squared batches at d 512/768/1024 take the int8 screen too; 4 (opt-in): bf16 screen only, and batches at 16 < k <= 256 take its wide form (K3c-W); 5 (opt-in): as 2, and BQ batches (k <= 256, d <= 4096) score on the int8 matrix cores (K5m); 6 (opt-in): as 2, and l2-squared PQ batches (k <= 256, dim % 32 = 0, dim / m 4 or 8, m <= 64, codebook image in LDS) take a bf16 MFMA screen + exact LUT rescore (K8m)
+	BatchScreen    int32  // 2: int8 screen (d 512/768/1024, else bf16) + exact rescore (default); 1: bf16; 0: exact only; 3 (opt-in): as 2, and l2-squared batches at d 512/768/1024 take the int8 screen too; 4 (opt-in): bf16 screen only, and batches at 16 < k <= 256 take its wide form (K3c-W); 5 (opt-in): as 2, and BQ batches (k <= 256, d <= 4096) score on the int8 matrix cores (K5m); 6 (opt-in): as 2, and l2-squared PQ batches (k <= 256, dim % 32 = 0, dim / m 4 or 8, m <= 64, codebook image in LDS) take a bf16 MFMA screen + exact LUT rescore (K8m); 7: as 6, and PQ codebooks K8m refuses for their size or segment count (dim % 64 = 0, dim <= 2048, dim / m 4 or 8) take K8m-S, the same screen in 64-dimension slices (opt-in)
 	Coalesce       int32  // 1: concurrent single-query searches of a corpus share launches (default)
 	HeapReplay     int32  // 1: BQ candidates / rescore exactly as Weaviate's heaps pick them (default)
 }

@@ -146,6 +146,21 @@ typedef struct wvg_options {
                                   17.6 against 30.9 ms; SLOWER at 100M k = 200 (1161 against 427 ms), with
                                   64 queries at 100M (k = 10 37.1 against 21.4 ms, k = 200 221 against
                                   25.8 ms) and at 1M x 128 (4.82 against 3.80 ms).
+                                  7 (opt-in): as 6 for everything 6 handles (F32 as 2, BQ on its default
+                                  route, K8m for every batch it accepts); in addition an l2-squared PQ
+                                  batch under 6's batch conditions whose codebook K8m refuses for its
+                                  image size or segment count takes K8m-S where dim % 64 = 0, dim <=
+                                  2048, dim / m is 4 or 8 and ks <= 256, for any m: the same screen,
+                                  bound, rescore and results, with the codebook image and the query
+                                  fragments passing through LDS in 64-dimension slices under fp32
+                                  accumulators carried in registers (101 KiB of LDS whatever the
+                                  codebook).  Dot / cosine PQ corpora and every other PQ call keep their
+                                  route.  Measured as 6 was (uniform random codes, alternating processes,
+                                  1024 queries, k = 10), 7 against the default route: 10M x 768 m = 96
+                                  46.9 against 286.0 ms (0.134 of the bf16 peak over the whole call), 10M
+                                  x 1536 m = 192 179.9 against 2038 ms, 10M x 384 m = 96 30.0 against
+                                  286.2 ms, 1M x 768 7.51 against 29.2 ms, 64 queries at 10M x 768 7.29
+                                  against 17.9 ms; SLOWER at 10M x 768 k = 200 (429.3 against 331.9 ms).
                                   The first screened search of a corpus allocates its shadow: int8 = dim
                                   + 8 bytes per row of capacity (7.7 GB at 10M x 768; its first build
                                   also takes one pass over the rows for the corpus scale and one host
@@ -432,7 +447,10 @@ int wvg_search_by_distance_window(wvg_corpus *c, const float *query, float targe
  * 8, the queries' fragments padded nq x dim x 2 and four constants of 4 bytes
  * per padded query, per query a bound and a flag-list entry of 4 bytes, per
  * (query, range) a count and a dropped bound of 4 bytes, and the rescan's partial
- * lists nq x 32 x k x 8 -- plus the queries' LUTs nq x m x ks x 4 as before.   */
+ * lists nq x 32 x k x 8 -- plus the queries' LUTs nq x m x ks x 4 as before.
+ * A batch_screen = 7 context: the same for K8m's batches, and the same layout
+ * with K8m-S's row ranges (whole 512-row blocks, at least four per range) for
+ * the batches K8m-S takes; never less than under 6.                           */
 size_t wvg_search_workspace_size(wvg_corpus *c, uint32_t nq, uint32_t k);
 int wvg_search_device(wvg_corpus *c, const float *d_queries, uint32_t nq, uint32_t k,
                       uint64_t *d_ids, float *d_dists, uint32_t *d_counts, void *d_workspace,
@@ -630,7 +648,8 @@ int wvg_search_device_pipelined_shadow(wvg_corpus *c, uint32_t nq, uint32_t k, u
  * allocated per corpus) and, in `reserved`, the row ranges the kernel splits
  * the corpus into (0 on every other route); and a PQ batch that takes K8m in a
  * batch_screen = 6 context (the option's conditions) reports matrix = 1, screen
- * = 1, shadow_bytes_per_row = 0 and its row ranges in `reserved`; every other PQ
+ * = 1, shadow_bytes_per_row = 0 and its row ranges in `reserved` (so does a
+ * batch that takes K8m or K8m-S in a batch_screen = 7 context); every other PQ
  * batch stays all zero.  shared_allow_list != 0: the
  * batch carries one allow list for all its queries; the route is the same.
  * Per-query allow windows never take the matrix path.                      */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Batched PQ ADC search: batch_screen = 6 (K8m, the bf16 MFMA screen over rows decoded in the kernel + the exact
-LUT rescore) against the default context (the parent route: one ADC scan per query, co-scheduled at m = 32) on
-one box.
+LUT rescore) or batch_screen = 7 (K8m-S as well: codebooks beyond LDS, --batch-screen 7 --shapes SLICE_SHAPES)
+against the default context (the parent route: one ADC scan per query, co-scheduled at m = 32) on one box.
 
 Every measurement is a fresh child process (this script with --child), and the two settings alternate shape by
 shape, so clock and cache state drift hits both alike.  A child sets a uniform codebook, fills the corpus with
@@ -13,7 +13,7 @@ included, so a lower bound of the screen launch's -- against the 2.5 PFLOP/s pea
 rows are not counted: the kernels have no counter for them.  Device API, queries in HBM.  Tooling only.
 
   tools/bench_pq_batch.py                      every shape of the issue (100M x 128, m = 32 needs ~4 GB of HBM)
-  tools/bench_pq_batch.py --shapes 10000000x128x32 --ks 10 --nqs 1024"""
+  tools/bench_pq_batch.py --batch-screen 7 --shapes slice      K8m-S's shapes (SLICE_SHAPES)"""
 import argparse
 import json
 import os
@@ -26,6 +26,10 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 # rows x dim x m : k list : nq list
 SHAPES = "100000000x128x32:10,200:1024,64;10000000x128x32:10:1024;1000000x128x32:10:1024;10000000x128x16:10:1024"
+# K8m-S (--batch-screen 7): 10M x 768 m = 96, 10M x 1536 m = 192, 10M x 384 m = 96 (dsub 4), 1M x 768; where K8m
+# lost: 64 queries, and k = 200, at 10M x 768
+SLICE_SHAPES = ("10000000x768x96:10:1024;10000000x1536x192:10:1024;10000000x384x96:10:1024;1000000x768x96:10:1024;"
+                "10000000x768x96:10:64;10000000x768x96:200:1024")
 PEAK_BF16 = 2.5e15
 
 
@@ -88,16 +92,18 @@ def main():
     ap.add_argument("--child", default="", help="(internal) one shape, one setting, in this process")
     ap.add_argument("--nq", type=int, default=1024)
     ap.add_argument("--k", type=int, default=10)
-    ap.add_argument("--batch-screen", type=int, default=6)
+    ap.add_argument("--batch-screen", type=int, default=6, help="6 (K8m) or 7 (K8m and K8m-S) against the default")
     a = ap.parse_args()
     if a.child:
         return child(a)
+    if a.shapes == "slice":
+        a.shapes = SLICE_SHAPES
     for spec in a.shapes.split(";"):
         shape, ks, nqs = spec.split(":")
         for k in ks.split(","):
             for nq in nqs.split(","):
                 for _ in range(a.rounds):
-                    for bs in (6, 2):  # a fresh process each: never a new program in one that holds the GPU
+                    for bs in (a.batch_screen, 2):  # a fresh process each: never a new program in one that holds the GPU
                         subprocess.run([sys.executable, os.path.abspath(__file__), "--child", shape, "--nq", nq,
                                         "--k", k, "--reps", str(a.reps), "--min-seconds", str(a.min_seconds),
                                         "--batch-screen", str(bs)], check=True)

@@ -167,8 +167,8 @@ bool ensure_shadow(wvg_corpus *c, hipStream_t s);
 inline bool shadow_wants_i8(const wvg_corpus *c)
 {
     const int bs = c->ctx->opt.batch_screen;
-    // (5 and 6 are 2 for every F32 corpus: they only move BQ batches to K5m, PQ batches to K8m)
-    return (c->metric == WVG_METRIC_L2 ? bs == 3 : bs == 2 || bs == 3 || bs == 5 || bs == 6) &&
+    // (5, 6 and 7 are 2 for every F32 corpus: they only move BQ batches to K5m, PQ batches to K8m / K8m-S)
+    return (c->metric == WVG_METRIC_L2 ? bs == 3 : bs == 2 || bs == 3 || bs == 5 || bs == 6 || bs == 7) &&
            wvg::screen_i8_supported(c->dim);
 }
 
@@ -233,7 +233,8 @@ SearchPlan plan_search(wvg_corpus *c, uint32_t nq, uint32_t k, const uint64_t *a
 // k <= 256, dim <= 4096, pools that fit -- and leaves every other plan as it is.
 void plan_bq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k);
 // K8m: the same for an l2-squared PQ batch with a codebook in a batch_screen = 6 context, where
-// pq_mfma_supported(dim, m, ks, k) holds and the pools fit.
+// pq_mfma_supported(dim, m, ks, k) holds and the pools fit; in a batch_screen = 7 context also K8m-S, where
+// pq_mfma_slice_supported holds instead (the launch tells the two apart by the same predicates).
 void plan_pq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k);
 uint32_t next_direction(wvg_corpus *c, uint32_t nq);
 int pq_dense(const wvg_corpus *c, const uint64_t *d_allow);

@@ -507,6 +507,11 @@ hipError_t launch_bq_mfma(const BqMfmaLaunch &L, hipStream_t s);
 constexpr uint32_t PQM_TAIL = 64 * 4 * 10 + 16;  // per-query constants, counts, bounds and the two flag words
 constexpr uint32_t PQM_FB_GROUPS = 32;           // workgroups of a flagged query's rescan
 bool pq_mfma_supported(uint32_t dim, uint32_t m, uint32_t ks, uint32_t k);
+// K8m-S (a batch_screen = 7 context): the same search where K8m refuses the codebook for its image size or its
+// segment count -- dim % 64 = 0, dim <= 2048, dsub in {4, 8}, any m: the image and the fragments pass through LDS
+// in 64-dimension slices under accumulators carried in registers.  Its row ranges are whole 512-row blocks.
+bool pq_mfma_slice_supported(uint32_t dim, uint32_t m, uint32_t ks, uint32_t k);
+uint32_t pq_mfma_slice_ranges(uint32_t nq, uint32_t k, uint64_t ntiles, int num_cus);
 void pq_mfma_prepare();  // the screen kernels' LDS limit, once per process (wvg_search_workspace_size, the launch)
 // alpha of K8m's bound: r is the sequential fp32 sum of m LUT entries, each go_step's chain over dsub elements
 __device__ __host__ inline double pq_mfma_alpha(uint32_t m, uint32_t dsub)

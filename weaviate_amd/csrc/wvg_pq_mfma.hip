@@ -1,5 +1,6 @@
 // wvg_pq_mfma.hip -- K8m: batched PQ ADC search on the bf16 matrix cores
-// (option batch_screen = 6; DESIGN section 5, "K8m").
+// (option batch_screen = 6; DESIGN section 5, "K8m"), and K8m-S, its form for codebooks beyond LDS
+// (option batch_screen = 7; below, above pqs_screen_kernel).
 //
 // For l2-squared the real-valued ADC distance of query q to a row with codes c is
 //     sum_s |q_s - C_s[c_s]|^2 = |q|^2 + |x^|^2 - 2 q.x^,   x^ = the row decoded from the codebook,
@@ -419,6 +420,347 @@ __global__ __launch_bounds__(PQM_WAVES * 64) void pqm_screen_kernel(PqmArgs a)
     compact(true, 0);
 }
 
+// ---- K8m-S: codebooks beyond LDS (option batch_screen = 7; DESIGN section 5, "K8m-S") ---------------------
+// The image and the query fragments pass through LDS in K slices of 64 dimensions (two K blocks): a slice's
+// image is ks * 128 contiguous bytes of [segment][code][dsub], its fragments 8 KiB of [nqb][dim / 32][NT][64],
+// and two slices are resident (slice s + 1 arrives by global_load_lds under the MFMAs of slice s; one
+// barrier per slice).  A workgroup takes its range in blocks of 8 tiles (512 rows); wave w owns tiles
+// 2 w, 2 w + 1 of the block and carries their 2 x 4 x 4 f32x4 accumulators (128 AGPRs) through every slice.
+// (Four tiles per wave, 256 accumulator registers, did not compile without a private segment: DESIGN.)  The
+// code chunk of a slice (dsub 4: one chunk per slice; dsub 8: one per two slices) is loaded into registers one
+// chunk ahead; a block's first chunk -- both chunks of rotated rows (m = 32, un-rotated at the head of the
+// block) -- arrives in LDS under the previous block's last chunk, so nothing stays in registers across the
+// epilogue.  The block's row norms are staged into LDS during slice 0.
+//
+// The bound.  Each accumulator is the C operand of its row tile's MFMAs in slice order, K block by K block:
+// the same fp32 chain over the d products as K8m's single K loop, nothing summed in another order and K never
+// split across waves.  So (b) above PqmArgs (K1q / K2q at d) holds as written, and with pq_mfma_alpha(m, dsub)
+// -- general in m -- so do (a), (c) and the three obligations.  PqmArgs serves both kernels: `ranges` are
+// K8m-S's block ranges here, every other field means what it means to K8m.
+//
+// The pools' step rule (a query's pool gains at most 256 keys between two compaction checks) is kept by
+// running the epilogue tile by tile: one tile per wave (256 rows per workgroup), then the barrier and the
+// flag check, twice per block.
+constexpr int PQS_TPW = 2;                                // tiles per wave and block
+constexpr int PQS_TB = PQM_WAVES * PQS_TPW;               // tiles per block
+constexpr uint32_t PQS_IMG = 32u << 10;                   // a slice's image at ks = 256
+constexpr uint32_t PQS_BUF = PQS_IMG + (8u << 10);        // + its 64 queries' fragments
+constexpr uint32_t PQS_NORMS = 2 * PQS_BUF;               // the block's row norms
+constexpr uint32_t PQS_CODES = PQS_NORMS + PQS_TB * 64 * 4;  // the block's first chunk (rotated rows: both)
+constexpr uint32_t PQS_TAIL = PQS_CODES + 2 * PQS_TB * 64 * 16;  // K8m's tail (PQM_TAIL)
+constexpr uint32_t PQS_LDS = PQS_TAIL + PQM_TAIL;
+constexpr uint32_t PQS_MAX_DIM = 2048;  // the largest dim taken: K1q's constant and alpha are checked up to it
+
+template <int DSUB, bool ROT>
+__global__ __launch_bounds__(PQM_WAVES * 64) void pqs_screen_kernel(PqmArgs a)
+{
+    constexpr int NT = PQM_NT, QB = PQM_QB, TPW = PQS_TPW;
+    constexpr int SPC = DSUB == 4 ? 1 : 2;  // slices per 16-code chunk
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *lnorm = reinterpret_cast<float *>(smem + PQS_NORMS);
+    uint4 *lcodes = reinterpret_cast<uint4 *>(smem + PQS_CODES);
+    float *ck1 = reinterpret_cast<float *>(smem + PQS_TAIL);  // [64] each, as in K8m
+    float *ck2 = ck1 + QB, *ccq = ck2 + QB, *cem = ccq + QB;
+    float *sig = cem + QB, *tadm = sig + QB, *wtau = tadm + QB;
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(wtau + QB), *wdrop = cnt + QB, *flag = wdrop + QB;  // flag[2] by tile parity
+
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint32_t rng, qb;  // K8m's block order
+    if (a.ranges % 8u == 0) {
+        const uint32_t kk = blockIdx.x >> 3;
+        rng = (kk / a.nqb) * 8u + (blockIdx.x & 7u);
+        qb = kk % a.nqb;
+    } else {
+        rng = blockIdx.x / a.nqb;
+        qb = blockIdx.x % a.nqb;
+    }
+    const uint32_t q0 = qb * QB, P = a.P, K = a.k, ks = a.ks, nch = a.nch;
+    const uint32_t S = a.dim / 64, slice_img = ks * 128u, nu_img = (slice_img + 1023u) / 1024u;
+    const uint32_t col = lane & 15u, g = lane >> 4;
+    const uint4 *gimg = a.image + lane;
+    const uint4 *gfr = a.qfrag + (size_t)qb * (a.dim / 32) * NT * 64 + lane;
+    // slice s into buffer s & 1, in 1 KiB units dealt over the waves (a unit = one wave-wide 16-byte load)
+    auto stage = [&](uint32_t s) {
+        unsigned char *dst = smem + (s & 1u) * PQS_BUF;
+        for (uint32_t u = wave; u < nu_img + 8u; u += PQM_WAVES) {
+            if (u < nu_img) {
+                if (u * 1024u + lane * 16u < slice_img)  // (ks % 8 != 0: the last unit is partial)
+                    __builtin_amdgcn_global_load_lds(gimg + ((size_t)s * slice_img + u * 1024u) / 16,
+                                                     reinterpret_cast<uint4 *>(dst + u * 1024u), 16, 0, 0);
+            } else {
+                const uint32_t v = u - nu_img;
+                __builtin_amdgcn_global_load_lds(gfr + ((size_t)s * 8 + v) * 64,
+                                                 reinterpret_cast<uint4 *>(dst + PQS_IMG + v * 1024u), 16, 0, 0);
+            }
+        }
+    };
+    const uint64_t nblk = (a.tile_end - a.tile_begin + PQS_TB - 1) / PQS_TB;
+    const uint64_t b0 = nblk * rng / a.ranges, b1 = nblk * (rng + 1) / a.ranges;
+    // chunk 0 (rotated rows: chunks 0 and 1) of the wave's tiles of block blk, a row per lane; each wave
+    // reads back only what it loaded.  (A tile past the end reads the range's last tile instead: its mask is 0
+    // and nothing of it is kept.)
+    auto stage_codes = [&](uint64_t blk) {
+#pragma unroll
+        for (int t = 0; t < TPW; t++) {
+            const uint64_t T = min(a.tile_begin + PQS_TB * blk + TPW * wave + t, a.tile_end - 1);
+#pragma unroll
+            for (int c = 0; c < (ROT ? 2 : 1); c++)
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4 *>(a.data) + ((size_t)T * nch + c) * 64 + lane,
+                                                 lcodes + (PQS_TB * c + TPW * wave + t) * 64, 16, 0, 0);
+        }
+    };
+    if (b0 < b1) {
+        stage(0);
+        stage_codes(b0);
+    }
+    if (tid < (uint32_t)QB) {
+        const bool live = q0 + tid < a.nq;  // a padding query admits nothing
+        ck1[tid] = a.k1[q0 + tid];
+        ck2[tid] = a.k2[q0 + tid];
+        ccq[tid] = a.cq[q0 + tid];
+        cem[tid] = a.emax[q0 + tid];
+        sig[tid] = live ? -__builtin_inff() : __builtin_inff();
+        tadm[tid] = live ? __builtin_inff() : -__builtin_inff();
+        wtau[tid] = __builtin_inff();
+        cnt[tid] = 0;
+        wdrop[tid] = 0xFFFFFFFFu;
+    }
+    if (tid < 2) flag[tid] = 0;
+    __syncthreads();
+
+    // K8m's compaction, word for word
+    auto compact = [&](bool last, uint32_t par) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the pools' stores
+        __threadfence_block();
+        __syncthreads();
+        if (tid == 0) flag[par] = 0;
+        for (uint32_t ql = wave; ql < (uint32_t)QB; ql += PQM_WAVES) {
+            const uint32_t q = q0 + ql;
+            if (q >= a.nq) break;
+            const uint32_t raw = cnt[ql];
+            if (!last && raw <= P - 256) continue;
+            float t = wtau[ql];
+            uint32_t kept = 0;
+            if (raw > 0) {
+                const uint64_t r = sc_compact(a.pools + ((size_t)q * a.ranges + rng) * P, min(raw, P), K, P - 256,
+                                              cem[ql], 0, t, (lds_u32 *)(wdrop + ql));
+                kept = (uint32_t)(r >> 32) & 0x7FFFFFFFu;
+                t = __uint_as_float((uint32_t)r);
+            }
+            if (lane == 0) {
+                if (raw > P) wdrop[ql] = 0;  // keys lost past the pool (never, by the step rule): always flagged
+                const uint32_t dr = wdrop[ql];
+                const float wt = dr == 0xFFFFFFFFu ? t : fminf(t, wvg_unord_f32(dr));
+                cnt[ql] = kept;
+                wtau[ql] = t;
+                tadm[ql] = wt;
+                sig[ql] = sc_sigma_l2(wt, ccq[ql]);
+                if (last) {
+                    a.pcnt[(size_t)q * a.ranges + rng] = kept;
+                    a.pdrop[(size_t)q * a.ranges + rng] = dr;
+                    if (t < __builtin_inff()) atomicMin(a.gbound + q, wvg_ord_f32(t));
+                }
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the packed pools
+        __threadfence_block();
+        __syncthreads();
+    };
+
+    // chunk c of rows 16 mt + col of the wave's tiles of block blk
+    auto load_chunk = [&](uint64_t blk, uint32_t c, u32x4 (&dst)[TPW][4]) {
+#pragma unroll
+        for (int t = 0; t < TPW; t++) {
+            const uint64_t T = min(a.tile_begin + PQS_TB * blk + TPW * wave + t, a.tile_end - 1);
+            const u32x4 *p = a.data + ((size_t)T * nch + c) * 64 + col;
+#pragma unroll
+            for (int mt = 0; mt < 4; mt++) dst[t][mt] = p[16 * mt];
+        }
+    };
+    for (uint64_t blk = b0; blk < b1; ++blk) {
+        const uint64_t T0 = a.tile_begin + PQS_TB * blk + TPW * wave;
+        uint64_t mask[TPW];
+#pragma unroll
+        for (int t = 0; t < TPW; t++) mask[t] = T0 + t < a.tile_end ? pqm_tile_mask(a, T0 + t) : 0ull;  // wave-uniform
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // slice 0 and the first chunk (this wave's own loads)
+        u32x4 cur[TPW][4], hi[TPW][4] = {};
+#pragma unroll
+        for (int t = 0; t < TPW; t++)
+#pragma unroll
+            for (int mt = 0; mt < 4; mt++) {
+                const uint4 x = lcodes[(TPW * wave + t) * 64 + 16 * mt + col];
+                cur[t][mt] = u32x4{x.x, x.y, x.z, x.w};
+                if constexpr (ROT) {
+                    const uint4 y = lcodes[(PQS_TB + TPW * wave + t) * 64 + 16 * mt + col];
+                    hi[t][mt] = u32x4{y.x, y.y, y.z, y.w};
+                }
+            }
+        if constexpr (ROT) {  // m = 32: back to segment order (stored byte b = code[(b + slot) mod 32])
+#pragma unroll
+            for (int t = 0; t < TPW; t++)
+#pragma unroll
+                for (int mt = 0; mt < 4; mt++) {
+                    const uint32_t w[8] = {cur[t][mt].x, cur[t][mt].y, cur[t][mt].z, cur[t][mt].w,
+                                           hi[t][mt].x, hi[t][mt].y, hi[t][mt].z, hi[t][mt].w};
+                    uint32_t o[8];
+                    pq32_window(w, (32u - ((16u * mt + col) & 31u)) & 31u, o);
+                    cur[t][mt] = u32x4{o[0], o[1], o[2], o[3]};
+                    hi[t][mt] = u32x4{o[4], o[5], o[6], o[7]};
+                }
+        }
+        f32x4 acc[TPW][4][NT];
+#pragma unroll
+        for (int t = 0; t < TPW; t++)
+#pragma unroll
+            for (int mt = 0; mt < 4; mt++)
+#pragma unroll
+                for (int nt = 0; nt < NT; nt++) acc[t][mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        __syncthreads();  // slice 0 is whole
+        for (uint32_t c = 0; c < nch; c++) {
+            u32x4 nxt[TPW][4] = {};
+            if (c + 1 == nch && blk + 1 < b1) stage_codes(blk + 1);  // (read back after this block's epilogue)
+            if constexpr (ROT) {
+#pragma unroll
+                for (int t = 0; t < TPW; t++)
+#pragma unroll
+                    for (int mt = 0; mt < 4; mt++) nxt[t][mt] = hi[t][mt];
+            } else if (c + 1 < nch) {
+                load_chunk(blk, c + 1, nxt);  // under this chunk's MFMAs
+            }
+#pragma unroll
+            for (int h = 0; h < SPC; h++) {
+                const uint32_t s = SPC * c + h;
+                if (s >= S) break;  // (a half-filled last chunk at dsub = 8)
+                if (s + 1 < S) stage(s + 1);
+                if (s == 0) {  // every wave is past the previous block's epilogue: the norms of this one
+#pragma unroll
+                    for (int t = 0; t < TPW; t++)
+                        if (T0 + t < a.tile_end)
+                            __builtin_amdgcn_global_load_lds(a.norms + (T0 + t - a.tile_begin) * 64 + lane,
+                                                             lnorm + (TPW * wave + t) * 64, 4, 0, 0);
+                }
+                const unsigned char *ib = smem + (s & 1u) * PQS_BUF;
+                const bf16x8 *bl = reinterpret_cast<const bf16x8 *>(ib + PQS_IMG);
+#pragma unroll
+                for (int kbl = 0; kbl < 2; kbl++) {
+                    bf16x8 b[NT];
+#pragma unroll
+                    for (int nt = 0; nt < NT; nt++) b[nt] = bl[(kbl * NT + nt) * 64 + lane];
+#pragma unroll
+                    for (int t = 0; t < TPW; t++) {
+                        if (mask[t] == 0ull) continue;
+                        bf16x8 af[4];
+#pragma unroll
+                        for (int mt = 0; mt < 4; mt++) {
+                            const u32x4 cw = cur[t][mt];
+                            if constexpr (DSUB == 4) {
+                                // the slice's segments 8 kbl + 2 g, + 1: the chunk's bytes 8 kbl + 2 g, + 1
+                                const uint64_t half = kbl ? ((uint64_t)cw.w << 32) | cw.z : ((uint64_t)cw.y << 32) | cw.x;
+                                const uint32_t hw = (uint32_t)(half >> (16u * g)) & 0xFFFFu;
+                                const uint32_t seg = 8u * kbl + 2u * g;
+                                const uint32_t c0 = min(hw & 0xFFu, ks - 1), c1 = min(hw >> 8, ks - 1);
+                                u32x2 lo = *reinterpret_cast<const u32x2 *>(ib + ((size_t)seg * ks + c0) * 8);
+                                u32x2 hi = *reinterpret_cast<const u32x2 *>(ib + ((size_t)(seg + 1) * ks + c1) * 8);
+                                const u32x4 v = {lo.x, lo.y, hi.x, hi.y};
+                                af[mt] = *reinterpret_cast<const bf16x8 *>(&v);
+                            } else {
+                                // the slice's segment 4 kbl + g: the chunk's byte 8 h + 4 kbl + g
+                                const uint32_t wj = h == 0 ? (kbl == 0 ? cw.x : cw.y) : (kbl == 0 ? cw.z : cw.w);
+                                const uint32_t seg = 4u * kbl + g;
+                                const uint32_t c0 = min((wj >> (8u * g)) & 0xFFu, ks - 1);
+                                af[mt] = *reinterpret_cast<const bf16x8 *>(ib + ((size_t)seg * ks + c0) * 16);
+                            }
+                        }
+#pragma unroll
+                        for (int mt = 0; mt < 4; mt++)
+#pragma unroll
+                            for (int nt = 0; nt < NT; nt++)
+                                acc[t][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], b[nt], acc[t][mt][nt], 0, 0, 0);
+                    }
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // slice s + 1, the norms, the next chunk
+                __syncthreads();                                   // and buffer s & 1 is free
+            }
+#pragma unroll
+            for (int t = 0; t < TPW; t++)
+#pragma unroll
+                for (int mt = 0; mt < 4; mt++) cur[t][mt] = nxt[t][mt];
+        }
+        if (blk + 1 < b1) stage(0);  // the next block's first slice under this block's epilogue
+        // K8m's epilogue, a tile at a time: element i of acc[t][mt][nt] is row 16 mt + 4 g + i of tile T0 + t
+        // against query 16 nt + col
+#pragma unroll
+        for (uint32_t t = 0; t < (uint32_t)TPW; t++) {
+            const uint32_t par = t & 1u;
+            const uint64_t m_t = mask[t];
+            if (m_t != 0ull) {
+                // tile t's accumulators against query tile nt (t is wave-uniform)
+                auto take = [&](int nt, f32x4 (&e)[4]) {
+#pragma unroll
+                    for (int mt = 0; mt < 4; mt++) e[mt] = acc[t][mt][nt];
+                };
+                f32x4 nv[4], hx[4];
+#pragma unroll
+                for (int mt = 0; mt < 4; mt++) {
+                    nv[mt] = *reinterpret_cast<const f32x4 *>(lnorm + (TPW * wave + t) * 64 + 16 * mt + 4 * g);
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        hx[mt][i] = nv[mt][i] <= 0x1p60f ? (nv[mt][i] * nv[mt][i]) * a.hg : __builtin_nanf("");
+                }
+                float k1r[NT], k2r[NT], sgr[NT];
+                bool any = false;
+#pragma unroll
+                for (int nt = 0; nt < NT; nt++) {
+                    k1r[nt] = ck1[16 * nt + col];
+                    k2r[nt] = ck2[16 * nt + col];
+                    sgr[nt] = sig[16 * nt + col];
+                    f32x4 e[4];
+                    take(nt, e);
+#pragma unroll
+                    for (int mt = 0; mt < 4; mt++)
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const float u = (e[mt][i] - hx[mt][i]) + __builtin_fmaf(nv[mt][i], k1r[nt], k2r[nt]);
+                            any |= !(u < sgr[nt]);
+                        }
+                }
+                if (__ballot(any) != 0ull) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; nt++) {
+                        const uint32_t ql = 16u * nt + col;
+                        if (q0 + ql >= a.nq) continue;
+                        f32x4 e[4];
+                        take(nt, e);
+#pragma unroll
+                        for (int mt = 0; mt < 4; mt++) {
+#pragma unroll
+                            for (int i = 0; i < 4; i++) {
+                                const float u =
+                                    (e[mt][i] - hx[mt][i]) + __builtin_fmaf(nv[mt][i], k1r[nt], k2r[nt]);
+                                const uint32_t row = 16u * mt + 4u * g + (uint32_t)i;
+                                if (!(u < sgr[nt]) && ((m_t >> row) & 1ull)) {
+                                    const float lower = sc_lower_l2(u, ccq[ql]);
+                                    if (!(lower > tadm[ql])) {
+                                        const uint32_t pos = atomicAdd(&cnt[ql], 1u);
+                                        if (pos < P)
+                                            a.pools[((size_t)(q0 + ql) * a.ranges + rng) * P + pos] =
+                                                ((uint64_t)wvg_ord_f32(lower) << 32) | (uint32_t)((T0 + t) * 64 + row);
+                                        if (pos + 256 >= P) flag[par] = 1u;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (flag[par] != 0u) compact(false, par);  // the same word for every wave: all compact or none
+        }
+    }
+    compact(true, 0);
+}
+
 // The exact rescore, in place: every kept (query, slot) gets K8's sum -- the call's LUT entries of
 // the row's codes added in segment order (pq_row_sum) -- as its key.
 __global__ __launch_bounds__(256) void pqm_rescore_keys_kernel(const uint4 *data, uint32_t nch, uint32_t m, uint32_t ks,
@@ -444,6 +786,16 @@ bool pq_mfma_supported(uint32_t dim, uint32_t m, uint32_t ks, uint32_t k)
     return (size_t)dim * ks * 2 + (size_t)dim * 2 * PQM_QB + PQM_TAIL <= WVG_LDS_BYTES;
 }
 
+// K8m-S takes what K8m refuses for its image size or segment count: whole 64-dimension slices, any m.
+bool pq_mfma_slice_supported(uint32_t dim, uint32_t m, uint32_t ks, uint32_t k)
+{
+    if (dim == 0 || m == 0 || ks == 0 || ks > 256 || k == 0 || k > 256 || dim % 64 != 0 || dim % m != 0 ||
+        dim > PQS_MAX_DIM)
+        return false;
+    const uint32_t dsub = dim / m;
+    return (dsub == 4 || dsub == 8) && !pq_mfma_supported(dim, m, ks, k);
+}
+
 static uint32_t pqm_pool(uint32_t k) { return screen_wide_pool(k); }
 
 uint32_t pq_mfma_ranges(uint32_t nq, uint32_t k, uint64_t ntiles, int num_cus)
@@ -458,6 +810,20 @@ uint32_t pq_mfma_ranges(uint32_t nq, uint32_t k, uint64_t ntiles, int num_cus)
     r = std::min<uint64_t>(r, (256ull << 20) / per_range);
     if (r >= 8) r -= r % 8;  // whole rounds over the 8 XCDs: the co-scheduled block order
     return (uint32_t)r;      // 0: the batch's pools do not fit (the caller keeps its route)
+}
+
+uint32_t pq_mfma_slice_ranges(uint32_t nq, uint32_t k, uint64_t ntiles, int num_cus)
+{
+    const uint32_t nqb = (nq + PQM_QB - 1) / PQM_QB;
+    const uint64_t nblk = (ntiles + PQS_TB - 1) / PQS_TB;
+    // one workgroup per CU; a range of at least 4 blocks (2048 rows, as K8m's)
+    uint64_t r = std::max<uint64_t>(1, (uint64_t)num_cus / nqb);
+    r = std::min(r, std::max<uint64_t>(1, nblk / 4));
+    // the pools of all workgroups within 256 MiB, as pq_mfma_ranges
+    const uint64_t per_range = (uint64_t)nqb * PQM_QB * pqm_pool(k) * 8;
+    r = std::min<uint64_t>(r, (256ull << 20) / per_range);
+    if (r >= 8) r -= r % 8;
+    return (uint32_t)r;
 }
 
 PqMfmaWs pq_mfma_ws(uint32_t nq, uint32_t k, uint32_t dim, uint32_t m, uint32_t ks, uint32_t ranges, uint64_t ntiles)
@@ -498,7 +864,13 @@ void pq_mfma_prepare()
         hipFuncSetAttribute(reinterpret_cast<const void *>(&pqm_screen_kernel<4>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)WVG_LDS_BYTES) == hipSuccess &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(&pqm_screen_kernel<8>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)WVG_LDS_BYTES) == hipSuccess;
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)WVG_LDS_BYTES) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&pqs_screen_kernel<4, false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQS_LDS) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&pqs_screen_kernel<8, false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQS_LDS) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&pqs_screen_kernel<8, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQS_LDS) == hipSuccess;
     (void)attr;
 }
 
@@ -506,7 +878,8 @@ hipError_t launch_pq_mfma(const PqMfmaLaunch &L, uint64_t *ids, float *dists, ui
 {
     const ScanArgs &sa = L.scan;
     const uint32_t nq = sa.nq, k = sa.k, m = sa.pq_m, ks = sa.pq_ks;
-    if (!pq_mfma_supported(L.dim, m, ks, k) || L.ranges == 0 || nq == 0 || sa.tile_end <= sa.tile_begin ||
+    const bool slice = pq_mfma_slice_supported(L.dim, m, ks, k);  // (never where K8m applies)
+    if (!(slice || pq_mfma_supported(L.dim, m, ks, k)) || L.ranges == 0 || nq == 0 || sa.tile_end <= sa.tile_begin ||
         sa.nchunks != pq_chunks(m) || sa.metric != WVG_M_L2)
         return hipErrorInvalidValue;
     const uint32_t dsub = L.dim / m, nqb = (nq + PQM_QB - 1) / PQM_QB, nq_pad = nqb * PQM_QB, P = pqm_pool(k);
@@ -558,7 +931,11 @@ hipError_t launch_pq_mfma(const PqMfmaLaunch &L, uint64_t *ids, float *dists, ui
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     pq_mfma_prepare();
-    if (dsub == 4) launch_timed((pqm_screen_kernel<4>), dim3(a.ranges * a.nqb), dim3(PQM_WAVES * 64), lds, s, a);
+    // (rotated rows, m = 32, reach K8m-S at dsub = 8 only: at dsub = 4 their image is K8m's)
+    if (slice && a.rot) launch_timed((pqs_screen_kernel<8, true>), dim3(a.ranges * a.nqb), dim3(PQM_WAVES * 64), PQS_LDS, s, a);
+    else if (slice && dsub == 4) launch_timed((pqs_screen_kernel<4, false>), dim3(a.ranges * a.nqb), dim3(PQM_WAVES * 64), PQS_LDS, s, a);
+    else if (slice) launch_timed((pqs_screen_kernel<8, false>), dim3(a.ranges * a.nqb), dim3(PQM_WAVES * 64), PQS_LDS, s, a);
+    else if (dsub == 4) launch_timed((pqm_screen_kernel<4>), dim3(a.ranges * a.nqb), dim3(PQM_WAVES * 64), lds, s, a);
     else launch_timed((pqm_screen_kernel<8>), dim3(a.ranges * a.nqb), dim3(PQM_WAVES * 64), lds, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     e = launch_collect_pools(a.pools, a.pcnt, a.pdrop, nq, L.ranges, P, k, a.emax, flist, nflag, a.gbound, s);

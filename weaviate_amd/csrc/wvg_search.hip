@@ -324,12 +324,16 @@ void plan_bq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k)
 void plan_pq_mfma(const wvg_corpus *c, SearchPlan &p, uint32_t nq, uint32_t k)
 {
     const uint32_t mn = c->ctx->opt.mfma_min_queries;
+    const int bs = c->ctx->opt.batch_screen;
     if (p.empty || c->kind != WVG_KIND_PQ || !c->d_centers || c->metric != WVG_METRIC_L2 ||
-        c->ctx->opt.batch_screen != 6 || mn == 0 || nq < mn || nq < 2 || p.allow_qstride != 0 ||
-        c->pq_ds * c->pq_m != c->dim || !pq_mfma_supported(c->dim, c->pq_m, c->pq_ks, k))
+        (bs != 6 && bs != 7) || mn == 0 || nq < mn || nq < 2 || p.allow_qstride != 0 || c->pq_ds * c->pq_m != c->dim)
         return;
+    // (7: K8m-S where K8m refuses the codebook)
+    const bool slice = bs == 7 && pq_mfma_slice_supported(c->dim, c->pq_m, c->pq_ks, k);
+    if (!slice && !pq_mfma_supported(c->dim, c->pq_m, c->pq_ks, k)) return;
     const uint64_t ntiles = std::max<uint64_t>(1, p.te - p.tb);
-    const uint32_t r = pq_mfma_ranges(nq, k, ntiles, c->ctx->num_cus);
+    const uint32_t r = slice ? pq_mfma_slice_ranges(nq, k, ntiles, c->ctx->num_cus)
+                             : pq_mfma_ranges(nq, k, ntiles, c->ctx->num_cus);
     if (r == 0) return;
     p.pqm = true;
     p.cosched = false;

@@ -577,7 +577,8 @@ func (x *Corpus) SearchBatch(qs []float32, nq, k int, allow helpers.AllowList) (
 // len(corpora)*dims floats) against corpora[i], the tenants of a multi-tenant
 // class, where every query names exactly one shard (adapters/repos/db/index.go:
 // 1516-1539) -- as one scan launch and one merge launch (wvg_search_group).  The
-// corpora are F32 corpora of one context, metric and dims; one may appear several
+// corpora are all F32 or all PQ corpora (one segment and centroid count, a codebook
+// each) of one context, metric and dims; one may appear several
 // times.  allows is empty (no query filtered) or holds one list per query: nil
 // means no filter for that query, a non-nil empty list an empty result for that
 // query alone (V/flat/index.go:423-427) -- the others are searched as usual.

@@ -304,9 +304,12 @@ int wvg_search(wvg_corpus *c, const float *queries, uint32_t nq, uint32_t k,
 /* nq flat.SearchByVector calls (V/flat/index.go:307-334), query i against
  * corpora[i] -- the shards of a multi-tenant class, one tenant per query
  * (adapters/repos/db/index.go:1516-1539, 1554-1565) -- in ONE scan launch and
- * one merge launch.  All corpora: kind F32, one context, one metric, one dim
- * (a class's tenants share its vector index config); a corpus may appear any
- * number of times.  queries [nq][dim].  allow_bits: NULL (no query filtered)
+ * one merge launch.  All corpora: one kind, F32 or PQ, one context, one metric,
+ * one dim (a class's tenants share its vector index config); a corpus may
+ * appear any number of times.  PQ tenants share (m, ks) and each has a
+ * codebook of its own: one more launch builds every query's lookup table
+ * against its own tenant's codebook.  BQ tenants: wvg_search_group_bq_rescore.
+ * queries [nq][dim].  allow_bits: NULL (no query filtered)
  * or nq pointers, entry i NULL or a bitmap over corpora[i]'s global docIDs of
  * allow_words[i] words (non-NULL with 0 words, or no allowed id in the
  * corpus: empty result for that query, as wvg_search).  k <= 256.

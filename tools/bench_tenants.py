@@ -13,6 +13,11 @@ as the rescore window.  The line then also holds, for a few queries, the rows th
 grouped filter keeps and the rows the heap inserts (recomputed on the host from
 the tenant's codes with weaviate_amd.flat.group_bq_kept_rows).
 
+With --compression pq every tenant is a PQ corpus of --pq-m segments x 256
+centroids with a random codebook of its own and uniform random codes (loaded as
+given, upsert_codes); the legs are those of `none`: a and b call wvg_search, c
+calls wvg_search_group.
+
 Per leg: per-call microseconds (p50 / p99), queries per second and, for c, the
 algorithmic time of a call (nq x rows x dim x 4 bytes at 8 TB/s).  --allow-frac
 gives every query an allow list of that fraction of its tenant's ids.  The legs
@@ -24,6 +29,7 @@ The product library, no tuning keys.  Examples:
   python tools/bench_tenants.py --allow-frac 0.1
   python tools/bench_tenants.py --tenants 64 --rows 100000 --dim 768 --metric cosine
   python tools/bench_tenants.py --compression bq --rescore-limit 200 --dim 1536
+  python tools/bench_tenants.py --compression pq --pq-m 32
 """
 import argparse
 import ctypes
@@ -86,7 +92,8 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--allow-frac", type=float, default=0.0)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--compression", default="none", choices=["none", "bq"])
+    ap.add_argument("--compression", default="none", choices=["none", "bq", "pq"])
+    ap.add_argument("--pq-m", type=int, default=32, help="with --compression pq: segments (256 centroids each)")
     ap.add_argument("--rescore-limit", type=int, default=200, help="with --compression bq: the rescore window")
     ap.add_argument("--kept-queries", type=int, default=4, help="with --compression bq: queries whose kept rows are counted")
     ap.add_argument("--out", default=None, help="also write the result line to this file")
@@ -94,7 +101,7 @@ def main():
     import torch
 
     torch.cuda.init()
-    from weaviate_amd._lib import KIND_BQ, KIND_F32, METRIC_BY_NAME, check, fptr, u32ptr, u64ptr
+    from weaviate_amd._lib import KIND_BQ, KIND_F32, KIND_PQ, METRIC_BY_NAME, check, fptr, u32ptr, u64ptr
     from weaviate_amd.device import Context, Corpus, allow_bitmap
 
     metric = METRIC_BY_NAME[a.metric]
@@ -104,9 +111,18 @@ def main():
     assert all(Q % x == 0 for x in nqs), "--queries must be a multiple of every nq"
     ctx = Context(0)
     lib = ctx.lib
-    bq, rl = a.compression == "bq", a.rescore_limit
-    tenants, codes = [], []  # the F32 corpora; with --compression bq the BQ corpora of the same rows
+    bq, pq, rl = a.compression == "bq", a.compression == "pq", a.rescore_limit
+    tenants, codes = [], []  # the F32 (pq: PQ) corpora; with --compression bq the BQ corpora of the same rows
+    rows_ids = np.arange(n, dtype=np.uint64)
     for t in range(a.tenants):
+        if pq:
+            assert d % a.pq_m == 0, "--dim must be a multiple of --pq-m"
+            trng = np.random.default_rng(1000 + t)
+            c = Corpus(ctx, KIND_PQ, metric, d, n)
+            c.set_codebook(trng.uniform(-1, 1, (a.pq_m, 256, d // a.pq_m)).astype(np.float32))
+            c.upsert_codes(rows_ids, trng.integers(0, 256, (n, a.pq_m), dtype=np.uint8))
+            tenants.append(c)
+            continue
         c = Corpus(ctx, KIND_F32, metric, d, n)
         c.fill_synthetic(1000 + t, n, 0)
         tenants.append(c)
@@ -232,6 +248,8 @@ def main():
 
     out = {"tenants": a.tenants, "rows": n, "dim": d, "metric": a.metric, "k": k, "queries": Q,
            "allow_frac": a.allow_frac, "threads": a.threads, "repeats": a.repeats, "legs": {}}
+    if pq:
+        out["compression"], out["pq_m"] = "pq", a.pq_m
     if bq:
         out["compression"], out["rescore_limit"] = "bq", rl
         out["kept_rows"] = kept_rows(codes, target, qs, allows, n, max(rl, k), a.kept_queries)
@@ -243,7 +261,8 @@ def main():
         if name.startswith("c"):
             nq = int(name[1:])
             e["nq"] = nq
-            row_bytes = (d + 127) // 128 * 16 if bq else d * 4  # the scanned rows: codes in 16-byte chunks, or floats
+            # the scanned rows: BQ / PQ codes in 16-byte chunks, or floats
+            row_bytes = (d + 127) // 128 * 16 if bq else ((a.pq_m + 15) // 16 * 16 if pq else d * 4)
             e["algorithmic_us_at_8TBs"] = round(nq * n * row_bytes / 8e12 * 1e6, 2)
         if name in checked:
             e["equals_leg_a"] = checked[name]

@@ -460,7 +460,8 @@ int wvgx_filtered_timing(uint64_t *out5, int reset)
 // blocks (first / second phase), 31 = filtered batches' windows from pinned staging, 32 = K3i's K3b pilot tiles,
 // 33 = screen ranges in whole rounds of the CUs, ..., 36 = the multi-GPU BQ flow's cross-slab bound,
 // 37 / 38 = the shared-row scan's sample tiles and the tiles-per-wave limit of seeding, 39 = its batched combine,
-// 40 = its bf16 screen (0 = every (query, tile) pair folded).
+// 40 = its bf16 screen (0 = every (query, tile) pair folded), ..., 43 / 44 = the grouped PQ search's item floor
+// (code bytes per LUT byte) and its items per CU.
 // Returns the previous value.
 int wvgx_set_tuning(int key, int value)
 {
@@ -595,6 +596,12 @@ int wvgx_set_tuning(int key, int value)
     } else if (key == 42) {
         old = t.qshare_shadow;
         t.qshare_shadow = value;
+    } else if (key == 43 && value >= 1) {
+        old = t.group_pq_floor;
+        t.group_pq_floor = value;
+    } else if (key == 44 && value >= 0) {
+        old = t.group_pq_items_per_cu;
+        t.group_pq_items_per_cu = value;
     }
     return old;
 }

@@ -25,29 +25,9 @@
 
 namespace wvg {
 
-// The tables, the queries, the validity words and the allow windows are written
-// before the launch and by nobody during it, and every index into them is
-// wave-uniform: read through the constant address space they are scalar loads
-// and the pointers, tile ranges and masks stay in SGPRs.  The pointers a
-// descriptor holds are global ones; saying so keeps the row loads global_load
-// (a pointer loaded from memory is a flat one to the compiler).
-typedef __attribute__((address_space(4))) const GroupQuery cgq;
-typedef __attribute__((address_space(4))) const GroupItem cgi;
-typedef __attribute__((address_space(4))) const uint64_t cgu64;
+// (cgq / cgi / cgu64 and group_tile_mask: wvg_internal.hpp, shared with wvg_group_pq.hip.)
 typedef __attribute__((address_space(4))) const float4 cgf4;
 typedef __attribute__((address_space(1))) const float4 ggf4;
-
-// Mask of live, allowed rows of tile t (tile_mask of wvg_scan.hip on the descriptor's scalars).
-__device__ __forceinline__ uint64_t group_tile_mask(cgu64 *valid, cgu64 *allow, bool filtered, uint64_t allow_words,
-                                                    uint64_t allow_t0, uint64_t t)
-{
-    uint64_t m = valid[t];
-    if (filtered) {
-        const uint64_t w = t - allow_t0;  // allow[0] is tile allow_t0's word
-        m &= w < allow_words ? allow[w] : 0ull;
-    }
-    return m;
-}
 
 template <int METRIC, int D, int E>
 __global__ __launch_bounds__(SCAN_WAVES * 64) void scan_f32_group_kernel(GroupArgs a)
@@ -189,10 +169,21 @@ int wvg_search_group(wvg_corpus *const *corpora, const float *queries, uint32_t 
             return fail(WVG_ERR_INVALID, "allow_bits[" + std::to_string(i) + "] without allow_words");
     }
     for (uint32_t i = 0; i < nq; i++)
-        if (corpora[i]->kind != WVG_KIND_F32)
-            return fail(WVG_ERR_UNSUPPORTED, "corpora[" + std::to_string(i) + "] is not an F32 corpus (grouped search: F32 only)");
-    if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "grouped search: k above 256");
+        if (corpora[i]->kind != WVG_KIND_F32 && corpora[i]->kind != WVG_KIND_PQ)
+            return fail(WVG_ERR_UNSUPPORTED, "corpora[" + std::to_string(i) +
+                                                 "] is neither an F32 nor a PQ corpus (grouped BQ search: wvg_search_group_bq_rescore)");
     wvg_corpus *c0 = corpora[0];
+    const bool pq = c0->kind == WVG_KIND_PQ;
+    for (uint32_t i = 0; i < nq; i++) {
+        const wvg_corpus *c = corpora[i];
+        const std::string at = "corpora[" + std::to_string(i) + "]";
+        if (c->kind != c0->kind) return fail(WVG_ERR_INVALID, at + " differs from corpora[0] in kind");
+        if (!pq) continue;
+        if (!c->d_centers) return fail(WVG_ERR_INVALID, at + ": PQ corpus has no codebook");
+        if (c->pq_m != c0->pq_m || c->pq_ks != c0->pq_ks || c->pq_ds != c0->pq_ds)
+            return fail(WVG_ERR_INVALID, at + " differs from corpora[0] in its PQ segments or centroids");
+    }
+    if (k > MAX_K) return fail(WVG_ERR_UNSUPPORTED, "grouped search: k above 256");
     wvg_ctx *ctx = c0->ctx;
     WVG_HIP(hipSetDevice(ctx->device));
 
@@ -242,7 +233,10 @@ int wvg_search_group(wvg_corpus *const *corpora, const float *queries, uint32_t 
         write_empty(nq, k, out_ids, out_dists, out_counts);
         return WVG_OK;
     }
-    const uint64_t T = group_item_tiles(total_tiles, ctx->num_cus);
+    // PQ: the scan form (LDS or global LUT, its workgroup size and residency) and its own item rule
+    const GroupPqForm form = pq ? group_pq_form(c0->pq_m, c0->pq_ks, k) : GroupPqForm{};
+    const uint64_t T = pq ? group_pq_item_tiles(total_tiles, ctx->num_cus, form, c0->pq_m, c0->pq_ks)
+                          : group_item_tiles(total_tiles, ctx->num_cus);
     uint64_t nlists_total = 0;
     for (uint32_t i = 0; i < nq; i++) {
         GroupQuery &d = desc[i];
@@ -257,13 +251,16 @@ int wvg_search_group(wvg_corpus *const *corpora, const float *queries, uint32_t 
     SlotGuard g(ctx);
     int rc = ctx->acquire(&g.slot);
     if (rc) return rc;
-    const uint32_t qpitch = f32_chunks(c0->dim) * 4;
-    // device scratch: the input block [queries | descriptors | items | allow windows], the lists, the results
+    const uint32_t qpitch = pq ? c0->dim : f32_chunks(c0->dim) * 4;
+    const uint32_t lpitch = pq ? (uint32_t)align_up((size_t)c0->pq_m * c0->pq_ks, 4) : 0;
+    // device scratch: the input block [queries | descriptors | items | allow windows | PQ: codebook pointers],
+    // the lists, the results, PQ: the queries' LUTs
     Carver in;
     const size_t i_q = in.take((size_t)nq * qpitch * 4);
     const size_t i_desc = in.take((size_t)nq * sizeof(GroupQuery));
     const size_t i_items = in.take((size_t)nitems * sizeof(GroupItem));
     const size_t i_allow = in.take((size_t)allow_total * 8);
+    const size_t i_cen = in.take(pq ? (size_t)nq * sizeof(float *) : 0);
     const size_t in_b = in.off;
     Carver cv;
     const size_t o_in = cv.take(in_b);
@@ -272,6 +269,7 @@ int wvg_search_group(wvg_corpus *const *corpora, const float *queries, uint32_t 
     const size_t o_d = cv.take((size_t)nq * k * 4);
     const size_t o_cnt = cv.take((size_t)nq * 4);
     const size_t out_b = o_cnt + (size_t)nq * 4 - o_ids;
+    const size_t o_lut = cv.take((size_t)nq * lpitch * 4);
     void *base = nullptr;
     rc = g.slot->device_scratch(cv.off, &base);
     if (rc) return rc;
@@ -282,7 +280,7 @@ int wvg_search_group(wvg_corpus *const *corpora, const float *queries, uint32_t 
     if (rc) return rc;
     char *hin = (char *)pinned, *hout = hin + in_b;
 
-    // queries as stage_queries / prepare_queries_host prepare them for an F32 corpus
+    // queries as stage_queries / prepare_queries_host prepare them for the corpus kind (PQ: at pitch dim)
     {
         std::vector<float> qf;
         std::vector<uint64_t> qb;
@@ -298,28 +296,53 @@ int wvg_search_group(wvg_corpus *const *corpora, const float *queries, uint32_t 
             items[at] = GroupItem{i, r, (uint32_t)(d.tile_begin + n * r / d.nlists),
                                   (uint32_t)(d.tile_begin + n * (r + 1) / d.nlists)};
         if (win[i]) std::memcpy(hin + i_allow + d.allow_off * 8, win[i], d.allow_words * 8);
+        if (pq) reinterpret_cast<const float **>(hin + i_cen)[i] = corpora[i]->d_centers;
     }
     std::memcpy(hin + i_desc, desc.data(), (size_t)nq * sizeof(GroupQuery));
 
     WVG_HIP(hipMemcpyAsync(b + o_in, hin, in_b, hipMemcpyHostToDevice, s));
-    GroupArgs a{};
-    a.desc = reinterpret_cast<const GroupQuery *>(b + o_in + i_desc);
-    a.items = reinterpret_cast<const GroupItem *>(b + o_in + i_items);
-    a.queries = reinterpret_cast<const float *>(b + o_in + i_q);
-    a.allow = reinterpret_cast<const uint64_t *>(b + o_in + i_allow);
-    a.partials = reinterpret_cast<uint64_t *>(b + o_part);
-    a.qpitch = qpitch;
-    a.k = k;
-    a.dim = c0->dim;
-    a.nchunks = c0->nchunks;
-    a.metric = c0->metric;
-    a.order512 = ctx->order512;
-    {
+    const GroupQuery *d_desc = reinterpret_cast<const GroupQuery *>(b + o_in + i_desc);
+    const GroupItem *d_items = reinterpret_cast<const GroupItem *>(b + o_in + i_items);
+    uint64_t *d_part = reinterpret_cast<uint64_t *>(b + o_part);
+    if (pq) {  // one launch for every query's LUT, then the scan (wvg_group_pq.hip)
+        GroupPqArgs pa{};
+        pa.desc = d_desc;
+        pa.items = d_items;
+        pa.centers = reinterpret_cast<const float *const *>(b + o_in + i_cen);
+        pa.queries = reinterpret_cast<const float *>(b + o_in + i_q);
+        pa.luts = reinterpret_cast<float *>(b + o_lut);
+        pa.allow = reinterpret_cast<const uint64_t *>(b + o_in + i_allow);
+        pa.partials = d_part;
+        pa.qpitch = qpitch;
+        pa.lpitch = lpitch;
+        pa.k = k;
+        pa.m = c0->pq_m;
+        pa.ks = c0->pq_ks;
+        pa.ds = c0->pq_ds;
+        pa.nchunks = c0->nchunks;
+        pa.metric = c0->metric;
+        WVG_HIP(launch_pq_lut_group(pa, nq, s));
+        ProfArm arm(ctx);  // wvg_profile_*: the scan dispatch's own events
+        if (arm.rc) return arm.rc;
+        WVG_HIP(launch_scan_pq_group(pa, form, nitems, s));
+    } else {
+        GroupArgs a{};
+        a.desc = d_desc;
+        a.items = d_items;
+        a.queries = reinterpret_cast<const float *>(b + o_in + i_q);
+        a.allow = reinterpret_cast<const uint64_t *>(b + o_in + i_allow);
+        a.partials = d_part;
+        a.qpitch = qpitch;
+        a.k = k;
+        a.dim = c0->dim;
+        a.nchunks = c0->nchunks;
+        a.metric = c0->metric;
+        a.order512 = ctx->order512;
         ProfArm arm(ctx);  // wvg_profile_*: the scan dispatch's own events
         if (arm.rc) return arm.rc;
         WVG_HIP(launch_scan_f32_group(a, nitems, s));
     }
-    WVG_HIP(launch_merge_group(a.desc, a.partials, nq, k, (uint64_t *)(b + o_ids), (float *)(b + o_d),
+    WVG_HIP(launch_merge_group(d_desc, d_part, nq, k, (uint64_t *)(b + o_ids), (float *)(b + o_d),
                                (uint32_t *)(b + o_cnt), s));
     WVG_HIP(hipMemcpyAsync(hout, b + o_ids, out_b, hipMemcpyDeviceToHost, s));
     WVG_HIP(hipStreamSynchronize(s));

@@ -199,6 +199,31 @@ __device__ __forceinline__ float pq_row_sum(const uint4 *rp, uint32_t nch, uint3
     }
     return sum;
 }
+// Step(a, b) in the pure-Go order: L2 D/l2.go:79-88, dot / cosine
+// D/dot_product.go:87-94, manhattan D/manhattan.go:68-78 (sum += |a-b|),
+// hamming D/hamming.go:76-86 (sum += 1 where a != b: Go's !=, a NaN counts).
+__device__ __forceinline__ float go_step(int metric, const float *a, const float *b, uint32_t n)
+{
+    float sum = 0.0f;
+    if (metric == WVG_M_L2) {
+        for (uint32_t i = 0; i < n; i++) {
+            float diff = a[i] - b[i];
+            float sq = diff * diff;
+            sum = sum + sq;
+        }
+    } else if (metric == WVG_M_MANHATTAN) {
+        for (uint32_t i = 0; i < n; i++) sum = sum + __builtin_fabsf(a[i] - b[i]);
+    } else if (metric == WVG_M_HAMMING) {
+        for (uint32_t i = 0; i < n; i++)
+            if (a[i] != b[i]) sum = sum + 1.0f;
+    } else {
+        for (uint32_t i = 0; i < n; i++) {
+            float p = a[i] * b[i];
+            sum = sum + p;
+        }
+    }
+    return sum;
+}
 size_t corpus_row_bytes(int kind, uint32_t dim, uint32_t pq_m);
 
 // f(std::integral_constant<int, M>{}) for the kernel template metric M of a
@@ -452,6 +477,26 @@ struct GroupItem {
     uint32_t query, range;   // range: the item's index among its query's lists
     uint32_t t0, t1;         // its tiles [t0, t1)
 };
+// The tables, the queries, the validity words and the allow windows are written
+// before the launch and by nobody during it, and every index into them is
+// wave-uniform: read through the constant address space they are scalar loads
+// and the pointers, tile ranges and masks stay in SGPRs.  The pointers a
+// descriptor holds are global ones; saying so keeps the row loads global_load
+// (a pointer loaded from memory is a flat one to the compiler).
+typedef __attribute__((address_space(4))) const GroupQuery cgq;
+typedef __attribute__((address_space(4))) const GroupItem cgi;
+typedef __attribute__((address_space(4))) const uint64_t cgu64;
+// Mask of live, allowed rows of tile t (tile_mask of wvg_scan.hip on the descriptor's scalars).
+__device__ __forceinline__ uint64_t group_tile_mask(cgu64 *valid, cgu64 *allow, bool filtered, uint64_t allow_words,
+                                                    uint64_t allow_t0, uint64_t t)
+{
+    uint64_t m = valid[t];
+    if (filtered) {
+        const uint64_t w = t - allow_t0;  // allow[0] is tile allow_t0's word
+        m &= w < allow_words ? allow[w] : 0ull;
+    }
+    return m;
+}
 struct GroupArgs {
     const GroupQuery *desc;  // [nq]
     const GroupItem *items;  // [gridDim.x]
@@ -466,6 +511,35 @@ hipError_t launch_merge_group(const GroupQuery *desc, const uint64_t *partials, 
                               float *dists, uint32_t *counts, hipStream_t s);
 // Tiles per work item (the item rule, DESIGN.md section 5 "Grouped search over tenants").
 uint32_t group_item_tiles(uint64_t total_tiles, int num_cus);
+// Grouped PQ search (wvg_group_pq.hip): the same descriptors, items and merge; every
+// query has a codebook of its own (centers[q]) and a LUT of its own (luts + q * lpitch,
+// built by pq_lut_group_kernel in the launch before the scan).
+struct GroupPqArgs {
+    const GroupQuery *desc;       // [nq]
+    const GroupItem *items;       // [gridDim.x] (scan)
+    const float *const *centers;  // [nq] the queries' codebooks [m][ks][ds]
+    const float *queries;         // [nq][qpitch], prepared (normalized for cosine)
+    float *luts;                  // [nq][lpitch]
+    const uint64_t *allow;        // the call's allow windows, back to back
+    uint64_t *partials;           // [lists][k]
+    uint32_t qpitch, lpitch;      // floats; lpitch = m * ks rounded up to 4 (16-byte transfers)
+    uint32_t k, m, ks, ds, nchunks;
+    int metric;
+};
+// The scan form of a call: which scan_pq_group_kernel<E, NC, GL> runs and what it occupies.
+struct GroupPqForm {
+    int e = 1, nc = 0;        // list registers; fixed 16-byte chunks per row (0 = generic)
+    bool gl = false;          // the LUT is read in global memory (no staging, no LDS request)
+    int waves = 16;           // workgroup size
+    uint32_t lds = 0;         // dynamic LDS bytes (the LUT)
+    int per_cu = 1;           // resident workgroups per CU (the runtime's occupancy figure)
+    void (*kernel)(GroupPqArgs) = nullptr;
+};
+GroupPqForm group_pq_form(uint32_t m, uint32_t ks, uint32_t k);
+// Tiles per work item (DESIGN.md section 5 "Grouped PQ search over tenants").
+uint32_t group_pq_item_tiles(uint64_t total_tiles, int num_cus, const GroupPqForm &f, uint32_t m, uint32_t ks);
+hipError_t launch_pq_lut_group(const GroupPqArgs &a, uint32_t nq, hipStream_t s);
+hipError_t launch_scan_pq_group(const GroupPqArgs &a, const GroupPqForm &f, uint32_t nitems, hipStream_t s);
 // ids KEY_NONE, dists +inf, counts 0 for nq queries (empty corpus / slab).
 hipError_t launch_fill_empty(uint64_t *ids, float *dists, uint32_t *counts, uint32_t nq, uint32_t k, hipStream_t s);
 hipError_t launch_scan_bq(const ScanArgs &a, uint64_t *partials, int groups, hipStream_t s);
@@ -870,6 +944,11 @@ struct Tuning {
     int qshare_shadow = 1;   // (tuning key 42) 1 = a screened shared-row launch reads the corpus's bf16 shadow and
                              // gathers fp32 only for admitted rows (scan_f32_qshare_shadow_kernel) where the
                              // shadow is there; 0 = always the fp32-screened kernel (A/B; profiles/r21/qshare_shadow/)
+    int group_pq_floor = 1;  // grouped PQ search (tuning key 43): an LDS-form work item holds at least this many
+                             // times its LUT's bytes in code bytes (group_pq_item_tiles; A/B 1 / 2 / 3 / 4 / 8,
+                             // profiles/tenants_pq/)
+    int group_pq_items_per_cu = 1;  // (tuning key 44) the item rule's ceiling term: items per CU a large call is
+                                    // cut into; 0 = two per resident workgroup, the F32 rule's (A/B)
     int multi_bq_bound = 1;  // multi-GPU BQ heap flow (tuning key 36): 1 = the cross-slab bound X_s in the filter,
                              // 0 = every slab filters with its own thresholds only (A/B: rows replayed)
     int screen_diag = 0;     // K3d / K3i diagnostics (tuning key 18, tools build only): 4 = the fast check but no

@@ -21,32 +21,6 @@ namespace wvg {
 
 constexpr int PQ_SCAN_WAVES = 16;  // K8: one workgroup per CU shares the LUT
 
-// Step(a, b) in the pure-Go order: L2 D/l2.go:79-88, dot / cosine
-// D/dot_product.go:87-94, manhattan D/manhattan.go:68-78 (sum += |a-b|),
-// hamming D/hamming.go:76-86 (sum += 1 where a != b: Go's !=, a NaN counts).
-__device__ __forceinline__ float go_step(int metric, const float *a, const float *b, uint32_t n)
-{
-    float sum = 0.0f;
-    if (metric == WVG_M_L2) {
-        for (uint32_t i = 0; i < n; i++) {
-            float diff = a[i] - b[i];
-            float sq = diff * diff;
-            sum = sum + sq;
-        }
-    } else if (metric == WVG_M_MANHATTAN) {
-        for (uint32_t i = 0; i < n; i++) sum = sum + __builtin_fabsf(a[i] - b[i]);
-    } else if (metric == WVG_M_HAMMING) {
-        for (uint32_t i = 0; i < n; i++)
-            if (a[i] != b[i]) sum = sum + 1.0f;
-    } else {
-        for (uint32_t i = 0; i < n; i++) {
-            float p = a[i] * b[i];
-            sum = sum + p;
-        }
-    }
-    return sum;
-}
-
 __global__ void pq_lut_kernel(int metric, const float *q, uint32_t nq, uint32_t qpitch, const float *centers,
                               uint32_t m, uint32_t ks, uint32_t ds, float *lut)
 {

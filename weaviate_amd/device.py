@@ -341,8 +341,9 @@ def _group_allows(allows, nq):
 
 
 def search_group(corpora, queries, k: int, allows=None):
-    """wvg_search_group: query i against corpora[i] (the tenants of one class: F32,
-    one context, one metric, one dim), all in one scan launch and one merge launch.
+    """wvg_search_group: query i against corpora[i] (the tenants of one class: all F32
+    or all PQ with one (m, ks) and a codebook each; one context, one metric, one dim),
+    all in one scan launch and one merge launch (PQ: one more for the lookup tables).
     allows: None, or one entry per query -- None (no filter) or a bitmap over that
     corpus's global docIDs (allow_bitmap; an empty array allows nothing).  Returns
     (ids [nq][k], dists [nq][k], counts [nq]), as nq Corpus.search calls would."""
